@@ -2,7 +2,12 @@
 """bench.py — BASELINE.json metric on config C2: batched 4K RGB -> 1080p Lanczos3
 resize (batch 256 uchar per GPU) through libmipx.so, device-resident input.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (the
+roofline object on it comes from the HIP events around the same K steps).  --full adds
+what takes runs of its own: the oracle check of the output, the centre-convention leg,
+the CPU baseline and the C1 CPU reference (each with its --no-* switch).
 
 One process per GPU (torchrun for N > 1, RANK/LOCAL_RANK/WORLD_SIZE from the
 env); requests are independent, so every rank runs its own batch with no
@@ -46,6 +51,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU (BASELINE C2: 256)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left in the output batch to "
+                         "DIR/<name>.npy as float32 (rank 0's batch; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also run the oracle check, the centre-convention leg, the CPU "
+                         "baseline and the C1 CPU reference (each can be switched off with its --no-* option)")
     ap.add_argument("--cpu-images", type=int, default=384, help="CPU baseline sample size (images): ~20 CPU-seconds on 16 EPYC cores")
     ap.add_argument("--cpu-distinct", type=int, default=24, help="distinct images in the CPU sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the CPUs allotted to this process")
@@ -58,7 +69,10 @@ def parse():
                     help="skip the second, centre-convention leg (the 'centre' object of the line)")
     ap.add_argument("--stub-step-ms", type=float, default=0.0,
                     help="harness test only: each step sleeps (rank + 1) x this many ms, no GPU work")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.batch < 1:
+        ap.error("--steps and --batch must be at least 1, --warmup at least 0")
+    return args
 
 
 def host_cores():
@@ -284,6 +298,33 @@ def verify_c2(d_in, d_out, n, sampling):
     return ok
 
 
+DUMP_WHOLE_ELEMS = 12 << 20  # float32 elements (48 MiB): a smaller output batch is written whole
+DUMP_SAMPLE_ELEMS = 1 << 21  # size of the seeded sample over a larger one
+DUMP_SEED = 20241220
+
+
+def dump_outputs(d_out, n, out_dir):
+    """--dump-outputs: the output batch as the last timed step left it (what a caller of
+    mipx_execute_dev receives), float32 .npy files, under 64 MB in all.  A small batch is
+    written whole (output.npy, n x H x W x B).  Of a larger one: its first and last image
+    whole (output_first.npy, output_last.npy) and output_sample.npy, the bytes at 2^21
+    flat positions of the n x H x W x B batch drawn once from numpy's default_rng(DUMP_SEED)
+    (the same positions in every run of the same --batch)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = d_out.numel()
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+    if total <= DUMP_WHOLE_ELEMS:
+        save("output", d_out.reshape(n, H_OUT, W_OUT, BANDS))
+        return
+    save("output_first", d_out[0].reshape(H_OUT, W_OUT, BANDS))
+    save("output_last", d_out[n - 1].reshape(H_OUT, W_OUT, BANDS))
+    pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE_ELEMS, dtype=np.int64))
+    save("output_sample", d_out.reshape(-1)[torch.from_numpy(pos).to(d_out.device)])
+
+
 def roofline(kernel, kern_ms, alg_bytes):
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
     traffic, traffic_src = pmc_traffic(kernel)
@@ -348,14 +389,17 @@ def main():
     wall_max = timed_region(timed_step, args.steps, 0, torch.cuda.synchronize, world)
     kern_ms = ev0.elapsed_time(ev1) / args.steps  # one kernel launch per step, on `stream`
 
+    if args.dump_outputs and rank == 0:  # before any later leg writes the output batch again
+        dump_outputs(d_out, n, args.dump_outputs)
+
     verify = None
-    if not args.no_verify and rank == 0:
+    if args.full and not args.no_verify and rank == 0:
         verify = verify_c2(d_in, d_out, n, sampling)
 
     # the other reduce sampling convention's kernel on the same batch, same process, after
     # the headline leg (PARITY_ASSUMPTIONS.md row 1 is unresolved: the line carries both)
     other = None
-    if not args.no_centre_leg and sampling == "corner":
+    if args.full and not args.no_centre_leg and sampling == "corner":
         ia.set_reduce_sampling("centre")
         try:
             cplan = ia.plan_make(ia.make_opts(width=W_OUT, height=H_OUT, embed=1),
@@ -388,7 +432,7 @@ def main():
         line["verified_vs_oracle"] = verify
         if other:
             line["centre"] = other
-        if not args.no_cpu and world == 1:  # the CPU figures are N = 1 figures
+        if args.full and not args.no_cpu and world == 1:  # the CPU figures are N = 1 figures
             line["cpu_baseline"] = cpu_baseline(args, sampling)
             line["cpu_baseline"]["sampling"] = sampling
             line["c1_cpu_reference"] = c1_cpu_reference(args, sampling)

@@ -4,7 +4,7 @@
 #   OUT=r04x STEPS="tests smoke bench configs stats pmc_c2 pmc_c3 survey" bash scripts/gpu_evidence.sh
 # tests   full -m gpu suite                 -> $O/pytest_gpu.log
 # smoke   __graft_entry__.smoke()            -> $O/smoke.log
-# bench   bench.py (N=1, driver launch path) -> $O/bench.json (+ bench_centre.json)
+# bench   bench.py --full (N=1, driver launch path) -> $O/bench.json (+ bench_centre.json)
 # configs bench_configs.py C3 C4 C5          -> $O/configs.jsonl
 # stats   rocprofv3 --kernel-trace --stats of bench.py and of each config -> $O/stats_*/
 # pmc_c2  FETCH_SIZE / WRITE_SIZE passes of bench.py at both samplings -> $O/traffic.json
@@ -26,16 +26,16 @@ for s in ${STEPS:-tests smoke bench configs}; do
              > "$O/pytest_gpu.log" 2>&1; tail -2 "$O/pytest_gpu.log" ;;
     smoke) run 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1; tail -2 "$O/smoke.log" ;;
     bench) run 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-             --master-port 29512 bench.py --gpus 1 --steps 100 --warmup 20 > "$O/bench.json" 2> "$O/bench.err"
-           run 300 python3 bench.py --steps 100 --warmup 20 --no-cpu --sampling centre > "$O/bench_centre.json" 2>> "$O/bench.err"
+             --master-port 29512 bench.py --gpus 1 --steps 100 --warmup 20 --full > "$O/bench.json" 2> "$O/bench.err"
+           run 300 python3 bench.py --steps 100 --warmup 20 --full --no-cpu --sampling centre > "$O/bench_centre.json" 2>> "$O/bench.err"
            cut -c1-240 "$O/bench.json" "$O/bench_centre.json" ;;
     configs) run 600 python3 -u bench_configs.py --configs C3,C4,C5 --steps 10 --warmup 2 > "$O/configs.jsonl" 2> "$O/configs.err"
              run 300 python3 -u bench_configs.py --configs C3 --steps 10 --warmup 2 --sampling centre \
                >> "$O/configs.jsonl" 2>> "$O/configs.err"; cut -c1-200 "$O/configs.jsonl" ;;
     stats) run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_c2" -o run -- \
-             python3 bench.py --steps 100 --warmup 20 --no-cpu > "$O/stats_c2.log" 2>&1
+             python3 bench.py --steps 100 --warmup 20 --full --no-cpu > "$O/stats_c2.log" 2>&1
            run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_c2_centre" -o run -- \
-             python3 bench.py --steps 100 --warmup 20 --no-cpu --sampling centre > "$O/stats_c2_centre.log" 2>&1
+             python3 bench.py --steps 100 --warmup 20 --full --no-cpu --sampling centre > "$O/stats_c2_centre.log" 2>&1
            for c in C3 C4 C5; do
              run 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_$c" -o run -- \
                python3 bench_configs.py --configs $c --steps 10 --warmup 2 > "$O/stats_$c.log" 2>&1

@@ -6,7 +6,7 @@ cd "$R"
 OUT="$R/gpurun_out/pmc_${TAG:-r01}"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="$R/bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu --no-verify ${BENCH_ARGS:-}"
+BENCH="$R/bench.py --steps ${STEPS:-3} --warmup 1 --full --no-cpu --no-verify ${BENCH_ARGS:-}"
 i=0
 while read -r ctrs; do
   [ -z "$ctrs" ] && continue

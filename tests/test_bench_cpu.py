@@ -52,6 +52,52 @@ def test_gpus_one_runs_in_process():
     assert d["n_gpus"] == 1 and 5 * 0.95 <= d["ms_per_step"]
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a small output batch is written whole; of a larger one the first and
+    last image whole plus a sample at seeded positions that are the same in every run.
+    float32, exact for bytes, under 64 MB in all."""
+    import numpy as np
+    import torch
+    img = bench.W_OUT * bench.H_OUT * bench.BANDS
+    g = torch.Generator().manual_seed(7)
+    small = torch.randint(0, 256, (2, img), dtype=torch.uint8, generator=g)
+    bench.dump_outputs(small, 2, str(tmp_path / "small"))
+    assert os.listdir(tmp_path / "small") == ["output.npy"]
+    whole = np.load(tmp_path / "small" / "output.npy")
+    assert whole.dtype == np.float32 and whole.shape == (2, bench.H_OUT, bench.W_OUT, bench.BANDS)
+    assert np.array_equal(whole.reshape(2, img), small.numpy())
+
+    big = torch.randint(0, 256, (3, img), dtype=torch.uint8, generator=g)
+    assert big.numel() > bench.DUMP_WHOLE_ELEMS
+    for d in ("a", "b"):
+        bench.dump_outputs(big, 3, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["output_first.npy", "output_last.npy", "output_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 10**6
+    a = {f: np.load(tmp_path / "a" / f) for f in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[f], np.load(tmp_path / "b" / f)) for f in names)
+    assert np.array_equal(a["output_first.npy"].reshape(-1), big[0].numpy())
+    assert np.array_equal(a["output_last.npy"].reshape(-1), big[2].numpy())
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, big.numel(), bench.DUMP_SAMPLE_ELEMS))
+    assert np.array_equal(a["output_sample.npy"], big.reshape(-1).numpy()[pos])
+    # a changed byte anywhere in the first or last image shows in the dump
+    big[2, img - 1] ^= 1
+    bench.dump_outputs(big, 3, str(tmp_path / "c"))
+    assert not np.array_equal(np.load(tmp_path / "c" / "output_last.npy"), a["output_last.npy"])
+
+
+def test_plain_run_options():
+    """--steps below 1 is an argument error, not a division by zero; --full is accepted
+    and --steps sets the number of timed steps the line reports."""
+    r = _run_bench(["--gpus", "1", "--steps", "0", "--stub-step-ms", "1"], timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+    r = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "0", "--stub-step-ms", "1", "--full"], timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] >= 0.95
+
+
 def test_gpus_disagreeing_with_world_size_is_an_error():
     """Under a launcher that set WORLD_SIZE, --gpus must match it: exit non-zero, no line."""
     r = _run_bench(["--gpus", "4", "--steps", "1", "--stub-step-ms", "1"],
