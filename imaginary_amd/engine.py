@@ -13,7 +13,8 @@ import numpy as np
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
                    EXTEND, GRAVITY, TYPES, sync_tuning)
 
-__all__ = ["DeviceBuffer", "make_opts", "make_input", "plan_make", "fit_dimension", "Engine",
+__all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
+           "make_opts", "make_input", "plan_make", "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
 SAMPLING = {"corner": 0, "centre": 1}
@@ -69,6 +70,139 @@ class DeviceBuffer:
             self.close()
         except Exception:
             pass
+
+
+def guard_damage(fill: int, before: np.ndarray, after: np.ndarray, nbytes: int):
+    """The pure comparison behind GuardedBuffer.check: `before` / `after` are the guard
+    bytes downloaded from in front of and behind a payload of `nbytes`, both expected to
+    be all `fill`.  None when they are; otherwise (first, last, count): the first and last
+    damaged offsets relative to the payload (before[-1] is offset -1, after[0] is offset
+    nbytes) and the number of damaged bytes."""
+    before = np.asarray(before, dtype=np.uint8).ravel()
+    after = np.asarray(after, dtype=np.uint8).ravel()
+    bad = np.concatenate([np.flatnonzero(before != fill) - before.size,
+                          np.flatnonzero(after != fill) + int(nbytes)])
+    if bad.size == 0:
+        return None
+    return int(bad[0]), int(bad[-1]), int(bad.size)
+
+
+class GuardedBuffer:
+    """A device payload of `nbytes` between two guard bands, in one allocation of
+    G + skew + nbytes + G bytes that starts out all `fill`; the payload begins at
+    base + G + skew.  G is a multiple of 4096, so with skew 0 the payload keeps the
+    alignment class of a plain allocation: 4096 * ceil((2 * row_bytes + 256) / 4096) for
+    an image buffer whose rows are `row_bytes` (w * bands) long, 4096 with row_bytes 0
+    (workspaces, the smartcrop origins).  check() finds bytes written into either band.
+    G is the detection window: a stray write further than G from the payload is not
+    seen (and is not safe either)."""
+
+    @staticmethod
+    def guard_bytes(row_bytes: int = 0) -> int:
+        return 4096 * -(-(2 * int(row_bytes) + 256) // 4096) if row_bytes else 4096
+
+    def __init__(self, nbytes: int, fill: int, row_bytes: int = 0, skew: int = 0, name: str = "buf",
+                 op: str = ""):
+        self.nbytes = int(nbytes)
+        self.fill = int(fill) & 0xFF
+        self.skew = int(skew)
+        self.name, self.op = name, op
+        self.guard = self.guard_bytes(row_bytes)
+        self.total = self.guard + self.skew + self.nbytes + self.guard
+        p = C.c_void_p()
+        check(lib.mipx_dev_malloc(C.byref(p), self.total), "mipx_dev_malloc")
+        self.base = p.value
+        self.ptr = self.base + self.guard + self.skew
+        check(lib.mipx_memset_dev(self.base, self.fill, self.total), "mipx_memset_dev")
+
+    def upload(self, a: np.ndarray) -> "GuardedBuffer":
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        assert a.nbytes == self.nbytes, (a.nbytes, self.nbytes)
+        check(lib.mipx_memcpy_h2d(self.ptr, a.ctypes.data, a.nbytes), "mipx_memcpy_h2d")
+        return self
+
+    def download(self, shape, dtype=np.uint8) -> np.ndarray:
+        out = np.empty(shape, dtype=dtype)
+        assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
+        check(lib.mipx_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes), "mipx_memcpy_d2h")
+        return out
+
+    def damage(self):
+        """guard_damage() of both bands as they are now (call after the synchronise)."""
+        before = np.empty(self.guard + self.skew, np.uint8)
+        after = np.empty(self.guard, np.uint8)
+        check(lib.mipx_memcpy_d2h(before.ctypes.data, self.base, before.nbytes), "mipx_memcpy_d2h")
+        check(lib.mipx_memcpy_d2h(after.ctypes.data, self.ptr + self.nbytes, after.nbytes), "mipx_memcpy_d2h")
+        return guard_damage(self.fill, before, after, self.nbytes)
+
+    def check(self, what: str = "") -> None:
+        d = self.damage()
+        if d is not None:
+            first, last, count = d
+            raise AssertionError(
+                f"{what or self.op}: guard of buffer '{self.name}' damaged: {count} byte(s), first at payload "
+                f"offset {first}, last at {last} (payload 0..{self.nbytes - 1}, fill 0x{self.fill:02X}, "
+                f"skew {self.skew})")
+
+    def close(self):
+        if getattr(self, "base", None):
+            lib.mipx_dev_free(self.base)
+            self.base = self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# (fill, skew_in, skew_out) while run_op / smartcrop_origins / execute guard their buffers; None = off
+_guard = None
+_guarded_calls = 0
+
+
+def set_guard(fill: Optional[int] = None, skew_in: int = 0, skew_out: int = 0):
+    """Footprint checking for run_op, smartcrop_origins and execute (tests; off by
+    default).  With a fill byte, every device buffer of a call (in / out / wm / ws /
+    origins) is a GuardedBuffer: output and workspace start as `fill`, the workspace is
+    exactly the advertised size, the input (skew_in) and output (skew_out) payloads start
+    that many bytes off the allocation's alignment, and every guard is checked before
+    the result is returned.  Returns the previous setting, which set_guard(*prev)
+    restores."""
+    global _guard
+    prev = _guard if _guard is not None else (None, 0, 0)
+    _guard = None if fill is None else (int(fill) & 0xFF, int(skew_in), int(skew_out))
+    return prev
+
+
+def guard_setting():
+    return _guard
+
+
+def guarded_calls() -> int:
+    """How many run_op / smartcrop_origins / execute calls have checked their guards."""
+    return _guarded_calls
+
+
+def _dev(name: str, op: str, nbytes: int, row_bytes: int = 0, data: Optional[np.ndarray] = None):
+    """One device buffer of a call: a plain DeviceBuffer, or a GuardedBuffer while
+    set_guard is on."""
+    if _guard is None:
+        return DeviceBuffer.from_array(data) if data is not None else DeviceBuffer(nbytes)
+    fill, skew_in, skew_out = _guard
+    skew = skew_in if name == "in" else skew_out if name == "out" else 0
+    b = GuardedBuffer(data.nbytes if data is not None else nbytes, fill, row_bytes, skew, name, op)
+    return b.upload(data) if data is not None else b
+
+
+def _check_guards(op: str, *bufs) -> None:
+    global _guarded_calls
+    if _guard is None:
+        return
+    for b in bufs:
+        if b is not None:
+            b.check(op)
+    _guarded_calls += 1
 
 
 def make_opts(**kw) -> MipxOpts:
@@ -211,8 +345,10 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
     sync_tuning()
     x = _batch(imgs)
     n, h, w, b = x.shape
-    din = DeviceBuffer.from_array(x)
+    what = f"mipx_op_{name}"
+    din = _dev("in", what, x.nbytes, w * b, x)
     ws = None
+    dwm = None
     wsb = 0
     if name == "reduce":
         hs, vs = p["hshrink"], p["vshrink"]
@@ -250,9 +386,9 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
         oh, ow, ob = h, w, (2 if b == 4 else 1 if b == 3 else b)
     else:
         raise ValueError(name)
-    dout = DeviceBuffer(n * oh * ow * ob)
+    dout = _dev("out", what, n * oh * ow * ob, ow * ob)
     if wsb:
-        ws = DeviceBuffer(wsb)
+        ws = _dev("ws", what, wsb)
     wsp = ws.ptr if ws else None
     if name == "reduce":
         code = lib.mipx_op_reduce(din.ptr, dout.ptr, n, w, h, b, hs, vs, wsp, wsb, None)
@@ -280,7 +416,7 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
         wm = np.ascontiguousarray(p["wm"], dtype=np.uint8)
         if wm.ndim == 2:
             wm = wm[:, :, None]
-        dwm = DeviceBuffer.from_array(wm)
+        dwm = _dev("wm", what, wm.nbytes, wm.shape[1] * wm.shape[2], wm)
         code = lib.mipx_op_watermark(din.ptr, dwm.ptr, dout.ptr, n, w, h, b, wm.shape[1], wm.shape[0],
                                      wm.shape[2], p["left"], p["top"], p["opacity"], None)
     elif name == "affine":
@@ -291,8 +427,9 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
         code = lib.mipx_op_flatten(din.ptr, dout.ptr, n, w, h, b, (C.c_int32 * 3)(*p["background"]), None)
     elif name == "bw":
         code = lib.mipx_op_colourspace_bw(din.ptr, dout.ptr, n, w, h, b, None)
-    check(code, f"mipx_op_{name}")
+    check(code, what)
     synchronize()
+    _check_guards(what, din, dout, dwm, ws)
     return dout.download((n, oh, ow, ob))
 
 
@@ -300,13 +437,14 @@ def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
     sync_tuning()
     x = _batch(imgs)
     n, h, w, b = x.shape
-    din = DeviceBuffer.from_array(x)
+    what = "mipx_op_smartcrop_origin"
+    din = _dev("in", what, x.nbytes, w * b, x)
     wsb = lib.mipx_op_workspace_bytes(7, n, w, h, b, cw, ch)
-    ws = DeviceBuffer(wsb)
-    org = DeviceBuffer(8 * n)
-    check(lib.mipx_op_smartcrop_origin(din.ptr, org.ptr, n, w, h, b, cw, ch, ws.ptr, wsb, None),
-          "mipx_op_smartcrop_origin")
+    ws = _dev("ws", what, wsb)
+    org = _dev("origins", what, 8 * n)
+    check(lib.mipx_op_smartcrop_origin(din.ptr, org.ptr, n, w, h, b, cw, ch, ws.ptr, wsb, None), what)
     synchronize()
+    _check_guards(what, din, ws, org)
     return org.download((n, 2), np.int32)
 
 
@@ -318,19 +456,28 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
     sync_tuning()
     x = _batch(imgs)
     n = x.shape[0]
-    din = DeviceBuffer.from_array(x)
-    dout = DeviceBuffer(n * plan.out_w * plan.out_h * plan.out_bands)
+    what = "mipx_execute_dev"
+    din = _dev("in", what, x.nbytes, x.shape[2] * x.shape[3], x)
+    dout = _dev("out", what, n * plan.out_w * plan.out_h * plan.out_bands, plan.out_w * plan.out_bands)
     wsb = lib.mipx_workspace_bytes(C.byref(plan), n)
-    ws = DeviceBuffer(wsb) if wsb else None
+    ws = _dev("ws", what, wsb) if wsb else None
     if junk is not None:
         check(lib.mipx_memset_dev(dout.ptr, junk, dout.nbytes), "mipx_memset_dev")
         if ws:
             check(lib.mipx_memset_dev(ws.ptr, junk, ws.nbytes), "mipx_memset_dev")
-    dwm = DeviceBuffer.from_array(wm) if wm is not None else None
+    dwm = None
+    if wm is not None:
+        wm = np.ascontiguousarray(wm, dtype=np.uint8)
+        dwm = _dev("wm", what, wm.nbytes, _wm_row_bytes(wm), wm)
     check(lib.mipx_execute_dev(C.byref(plan), n, din.ptr, dout.ptr, dwm.ptr if dwm else None,
-                               ws.ptr if ws else None, wsb, None), "mipx_execute_dev")
+                               ws.ptr if ws else None, wsb, None), what)
     synchronize()
+    _check_guards(what, din, dout, dwm, ws)
     return dout.download((n, plan.out_h, plan.out_w, plan.out_bands))
+
+
+def _wm_row_bytes(wm: np.ndarray) -> int:
+    return int(wm.shape[1] * (wm.shape[2] if wm.ndim == 3 else 1)) if wm.ndim >= 2 else int(wm.size)
 
 
 def _vips_round(v: float) -> int:

@@ -29,6 +29,13 @@
  *    batch of n equally sized images packed back to back, and a hipStream_t
  *    passed as void* (NULL = the device's default engine stream).  They only
  *    enqueue work; they never synchronise or allocate.
+ *  - Footprint of those entry points (pinned by tests/test_footprint_gpu.py): they
+ *    read only the n * w * h * bands input bytes and the watermark image, and write
+ *    only the output bytes and the first mipx_[op_]workspace_bytes() bytes of the
+ *    workspace.  The image pointers may have any byte alignment, with one exception:
+ *    on 4-band images mipx_op_rot and mipx_op_embed (and mipx_op_flip on images of
+ *    2 GiB or more, or more than 65535 rows), per op or as a plan step, take 4-byte
+ *    aligned input and output pointers only and return MIPX_EINVAL for others.
  *  - Thread-safe: mipx_submit / mipx_wait / mipx_process may be called from
  *    many threads (one goroutine per HTTP request).
  */

@@ -6,6 +6,7 @@ tiles (extend mode per byte), every extend mode, unaligned output rows, scales b
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
 from test_parity_gpu import assert_same, rand_img, smooth_img
 
 pytestmark = pytest.mark.gpu

@@ -9,6 +9,7 @@ not a multiple of 16 bytes.  Every case also through the kernels behind it
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
 from test_parity_gpu import assert_same, rand_img, smooth_img
 
 pytestmark = pytest.mark.gpu

@@ -10,6 +10,8 @@ k_rchain, measured slower, was removed in r06: profiles/r05/c3_chain_ab.jsonl.)
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 # (w, h, bands, stage-2 opts): the C3 shape scaled down, full-output windows (rows above

@@ -13,6 +13,7 @@ planner's plan through ref_execute on the same image.
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
 import workloads
 
 pytestmark = pytest.mark.gpu

@@ -7,6 +7,7 @@ Reference: image.go:379-410 (/pipeline), :171-189 (Crop)."""
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
 import imaginary_amd as ia
 
 # every case under both reduce sampling conventions (the centre one runs k_reduce2m)

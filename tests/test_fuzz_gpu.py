@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 # MIPX_FUZZ_SEEDS widens the run (e.g. 400 for a long soak on the GPU box)
 SEEDS = int(os.environ.get("MIPX_FUZZ_SEEDS", "24"))

@@ -6,6 +6,8 @@ not model — see PARITY_ASSUMPTIONS.md)."""
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 

@@ -10,6 +10,7 @@ tiles read back by tile_rd_lane (r06, MIPX_RCOL_TRL=0: lane / 4)."""
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
 from test_parity_gpu import assert_same, rand_img, smooth_img
 
 pytestmark = pytest.mark.gpu

@@ -4,6 +4,8 @@ width, edge strips, windows (reduce -> extract), the config shapes."""
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 CASES = [  # h, w, b, hs, vs

@@ -10,6 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from footprint import guarded  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 
