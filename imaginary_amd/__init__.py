@@ -8,7 +8,8 @@ from ._abi import lib, MipxError, MipxPlan, MipxOpts, MipxInput, LIB_PATH, TYPES
 from ._abi import (MIPX_OK, MIPX_EINVAL, MIPX_EUNSUPPORTED, MIPX_ENOMEM, MIPX_ENODEV, MIPX_EDEVICE,  # noqa: F401
                    MIPX_ETIMEOUT, MIPX_ENOTINIT, MIPX_ESTALE, MIPX_EBUSY)
 from .engine import (DeviceBuffer, Engine, GuardedBuffer, device_count, execute, fit_dimension,  # noqa: F401
-                     guard_damage, guard_setting, guarded_calls, make_input, make_opts, plan_chain, plan_make,
-                     reduce_sampling, run_op, set_guard, set_reduce_sampling, smartcrop_origins, synchronize)
+                     guard_damage, guard_setting, guarded_calls, make_input, make_opts, plan_add_textmark, plan_chain,
+                     plan_make, plan_textmark_geometry, reduce_sampling, run_op, set_guard, set_reduce_sampling,
+                     smartcrop_origins, synchronize)
 
 __version__ = "0.2.0"

@@ -118,6 +118,63 @@ def decode(buf: bytes, shrink: int = 1) -> np.ndarray:
     return a[:, :, None] if a.ndim == 2 else np.ascontiguousarray(a)
 
 
+_SANS_FACES = ("DejaVuSans.ttf", "LiberationSans-Regular.ttf", "NotoSans-Regular.ttf", "FreeSans.ttf", "Arial.ttf")
+DEFAULT_FONT_POINTS = 10.0
+
+
+def _sans_face(pixels: int):
+    try:
+        from PIL import ImageFont
+    except ImportError as e:
+        raise CodecError("no text renderer (Pillow) available") from e
+    for name in _SANS_FACES:
+        try:
+            return ImageFont.truetype(name, pixels)
+        except OSError:      # face not installed
+            continue
+        except ImportError as e:   # Pillow built without FreeType
+            raise CodecError(f"no text renderer: {e}") from e
+    raise CodecError("no text renderer: no sans TrueType face found")
+
+
+def render_text(text: str, font: str = "sans 10", width: int = 0, dpi: int = 150) -> np.ndarray:
+    """Opt-in stand-in for vips_text (the renderer imaginary.Watermark takes): the tight
+    1-band coverage mask, (h, w) uint8, of `text` in a system sans face, wrapped at spaces to
+    `width` pixels (0 = no wrapping).  `font` is a pango description; only its trailing
+    point size is read, and the glyphs are points * dpi / 72 pixels high.  Pillow's
+    FreeType rasteriser is not pango: the pixels differ from libvips', as Pillow's codecs
+    differ from libvips' savers."""
+    words = font.split()
+    try:
+        points = float(words[-1]) if words else DEFAULT_FONT_POINTS
+    except ValueError:
+        points = DEFAULT_FONT_POINTS
+    face = _sans_face(max(1, int(round(points * dpi / 72.0))))
+    from PIL import Image as PILImage, ImageDraw
+    lines = []
+    for para in text.split("\n"):
+        line = ""
+        for word in para.split(" "):
+            trial = word if not line else line + " " + word
+            if width > 0 and line and face.getlength(trial) > width:
+                lines.append(line)
+                line = word
+            else:
+                line = trial
+        lines.append(line)
+    body = "\n".join(lines)
+    probe = ImageDraw.Draw(PILImage.new("L", (1, 1)))
+    l, t, r, b = probe.multiline_textbbox((0, 0), body, font=face)
+    if r <= l or b <= t:
+        raise CodecError("text watermark: nothing to render")
+    im = PILImage.new("L", (r - l, b - t), 0)
+    ImageDraw.Draw(im).multiline_text((-l, -t), body, fill=255, font=face)
+    box = im.getbbox()
+    if box is None:
+        raise CodecError("text watermark: nothing to render")
+    return np.ascontiguousarray(np.asarray(im.crop(box), dtype=np.uint8))
+
+
 def encode(px: np.ndarray, t: str, quality: Optional[int] = None, compression: Optional[int] = None) -> bytes:
     """Encode (h, w, bands) uint8 pixels as type t."""
     if _PIL is None:

@@ -217,6 +217,9 @@ int bw_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int b, hipSt
 // k_composite.hip
 int watermark_launch(const uint8_t *base, const uint8_t *wm, uint8_t *out, int n, int w, int h, int bands, int ww,
                      int wh, int wb, int left, int top, float opacity, hipStream_t st);
+// k_textmark.hip: the rendered text mask (tw x th x 1) tiled and blended in; 1 or 3 bands -> 3
+int textmark_launch(const uint8_t *in, const uint8_t *mask, uint8_t *out, int n, int w, int h, int bands, int tw,
+                    int th, int margin, float opacity, const int *colour, hipStream_t st);
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,

@@ -127,6 +127,17 @@ int mipx_op_watermark(const uint8_t *d_base, const uint8_t *d_wm, uint8_t *d_out
     return watermark_launch(d_base, d_wm, d_out, n, w, h, bands, ww, wh, wb, left, top, opacity, as_stream(stream));
 }
 
+int mipx_op_text_watermark(const uint8_t *d_in, const uint8_t *d_mask, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                           int32_t bands, int32_t mask_w, int32_t mask_h, int32_t margin, float opacity,
+                           const int32_t *colour3, void *stream) {
+    if (!d_in || !d_mask || !d_out || !colour3 || !geom_ok(n, w, h, bands) || mask_w <= 0 || mask_h <= 0 || margin < 0)
+        return MIPX_EINVAL;
+    for (int z = 0; z < 3; ++z)
+        if (colour3[z] < 0 || colour3[z] > 255) return MIPX_EINVAL;
+    return textmark_launch(d_in, d_mask, d_out, n, w, h, bands, mask_w, mask_h, margin, opacity, colour3,
+                           as_stream(stream));
+}
+
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t bands, double xscale,
                    double yscale, int32_t extend, void *stream) {
     if (!d_in || !d_out || !geom_ok(n, w, h, bands) || !(xscale > 0) || !(yscale > 0)) return MIPX_EINVAL;

@@ -535,6 +535,79 @@ extern "C" int mipx_plan_make(const mipx_opts *opts, const mipx_input *in, mipx_
     return MIPX_OK;
 }
 
+// ---- text watermark (bimg watermarkImageWithText) --------------------------------
+// bimg's resizer order: applyEffects (blur), then watermarkImageWithText, then
+// watermarkImageWithAnotherImage, imageFlatten and the save-time colourspace.  In a
+// mipx_plan_make plan those last three are the trailing WATERMARK / FLATTEN / BW steps.
+namespace {
+
+int textmark_index(const mipx_plan *p) {
+    int i = p->n_steps;
+    if (i > 0 && p->steps[i - 1].op == MIPX_OP_BW) --i;
+    if (i > 0 && p->steps[i - 1].op == MIPX_OP_FLATTEN) --i;
+    if (i > 0 && p->steps[i - 1].op == MIPX_OP_WATERMARK) --i;
+    return i;
+}
+
+bool plan_header_ok(const mipx_plan *p) {
+    return p && p->n_steps >= 0 && p->n_steps <= MIPX_MAX_STEPS && p->in_w > 0 && p->in_h > 0 && p->in_bands >= 1 &&
+           p->in_bands <= 4;
+}
+
+}  // namespace
+
+extern "C" int mipx_plan_textmark_geometry(const mipx_plan *plan, int32_t *w, int32_t *h, int32_t *bands) {
+    if (!plan_header_ok(plan) || !w || !h || !bands) return MIPX_EINVAL;
+    const int at = textmark_index(plan);
+    *w = at ? plan->steps[at - 1].out_w : plan->in_w;
+    *h = at ? plan->steps[at - 1].out_h : plan->in_h;
+    *bands = at ? plan->steps[at - 1].out_bands : plan->in_bands;
+    return MIPX_OK;
+}
+
+extern "C" int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t mask_h, int32_t margin, float opacity,
+                                      const int32_t *colour3, int32_t no_replicate) {
+    if (!plan_header_ok(plan) || !colour3 || mask_w <= 0 || mask_h <= 0 || margin < 0) return MIPX_EINVAL;
+    for (int z = 0; z < 3; ++z)
+        if (colour3[z] < 0 || colour3[z] > 255) return MIPX_EINVAL;
+    if (no_replicate) {  // bimg leaves the replicated-mask slot unset there: not restated
+        mipx::set_error("text watermark with NoReplicate is not implemented");
+        return MIPX_EUNSUPPORTED;
+    }
+    for (int i = 0; i < plan->n_steps; ++i)
+        if (plan->steps[i].op == MIPX_OP_WATERMARK || plan->steps[i].op == MIPX_OP_TEXTMARK) {
+            mipx::set_error("the plan already has a watermark step (one watermark image per request)");
+            return MIPX_EUNSUPPORTED;
+        }
+    int32_t w, h, b;
+    const int at = textmark_index(plan);
+    mipx_plan_textmark_geometry(plan, &w, &h, &b);
+    if (b != 1 && b != 3) {  // vips_ifthenelse: 3-band colour against 2 or 4 bands
+        mipx::set_error("text watermark on a %d-band image", b);
+        return MIPX_EUNSUPPORTED;
+    }
+    if (b == 1 && at < plan->n_steps) {  // the later steps were planned for 1 band
+        mipx::set_error("text watermark on a 1-band image with steps after it");
+        return MIPX_EUNSUPPORTED;
+    }
+    if (plan->n_steps >= MIPX_MAX_STEPS) {
+        mipx::set_error("mipx_plan_add_textmark: the plan is full (MIPX_MAX_STEPS)");
+        return MIPX_EINVAL;
+    }
+    for (int i = plan->n_steps; i > at; --i) plan->steps[i] = plan->steps[i - 1];
+    ++plan->n_steps;
+    mipx_step &s = plan->steps[at];
+    std::memset(&s, 0, sizeof(s));
+    s.op = MIPX_OP_TEXTMARK;
+    s.a[0] = mask_w, s.a[1] = mask_h, s.a[2] = margin;
+    s.a[3] = colour3[0], s.a[4] = colour3[1], s.a[5] = colour3[2];
+    // watermarkImageWithText: Opacity 0 -> 0.25, above 1 -> 1 (float32, as bimg keeps it)
+    s.d[0] = opacity == 0.0f ? 0.25 : (opacity > 1.0f ? 1.0 : static_cast<double>(opacity));
+    s.out_w = w, s.out_h = h, s.out_bands = 3;
+    if (at + 1 == plan->n_steps) plan->out_bands = 3;
+    return MIPX_OK;
+}
+
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {
     if (!stages || !out || n_stages <= 0) return MIPX_EINVAL;
     mipx_plan m{};
@@ -554,7 +627,8 @@ extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_p
             return MIPX_EINVAL;
         }
         bool wm = false;
-        for (int i = 0; i < s.n_steps; ++i) wm |= s.steps[i].op == MIPX_OP_WATERMARK;
+        for (int i = 0; i < s.n_steps; ++i)
+            wm |= s.steps[i].op == MIPX_OP_WATERMARK || s.steps[i].op == MIPX_OP_TEXTMARK;
         wm_stages += wm;
         if (wm_stages > 1) {
             mipx::set_error("mipx_plan_chain: more than one watermark stage");

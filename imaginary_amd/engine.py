@@ -14,7 +14,8 @@ from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, 
                    EXTEND, GRAVITY, TYPES, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
-           "make_opts", "make_input", "plan_make", "fit_dimension", "Engine",
+           "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
+           "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
 SAMPLING = {"corner": 0, "centre": 1}
@@ -245,6 +246,25 @@ def plan_chain(stages) -> MipxPlan:
     return p
 
 
+def plan_textmark_geometry(plan: MipxPlan):
+    """mipx_plan_textmark_geometry: (w, h, bands) of the image where a text watermark
+    step would go (after the blur, before the watermark image, flatten and B_W)."""
+    w, h, b = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.mipx_plan_textmark_geometry(C.byref(plan), C.byref(w), C.byref(h), C.byref(b)),
+          "mipx_plan_textmark_geometry")
+    return w.value, h.value, b.value
+
+
+def plan_add_textmark(plan: MipxPlan, mask_w: int, mask_h: int, margin: int, opacity: float,
+                      colour=(0, 0, 0), no_replicate: bool = False) -> MipxPlan:
+    """mipx_plan_add_textmark on `plan` (in place; returned for convenience): the rendered
+    text mask then travels as the request's watermark image."""
+    check(lib.mipx_plan_add_textmark(C.byref(plan), mask_w, mask_h, margin, opacity,
+                                     (C.c_int32 * 3)(*list(colour)[:3]), int(bool(no_replicate))),
+          "mipx_plan_add_textmark")
+    return plan
+
+
 def fit_dimension(iw, ih, fw, fh):
     a, b = C.c_int32(), C.c_int32()
     check(lib.mipx_fit_dimension(iw, ih, fw, fh, C.byref(a), C.byref(b)), "mipx_fit_dimension")
@@ -375,6 +395,8 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
     elif name == "watermark":
         oh, ow = h, w
         ob = b if b in (2, 4) else b + 1
+    elif name == "textmark":
+        oh, ow, ob = h, w, 3
     elif name == "affine":
         import math
         ow, oh, ob = int(math.ceil(w * p["xscale"])), int(math.ceil(h * p["yscale"])), b
@@ -419,6 +441,11 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
         dwm = _dev("wm", what, wm.nbytes, wm.shape[1] * wm.shape[2], wm)
         code = lib.mipx_op_watermark(din.ptr, dwm.ptr, dout.ptr, n, w, h, b, wm.shape[1], wm.shape[0],
                                      wm.shape[2], p["left"], p["top"], p["opacity"], None)
+    elif name == "textmark":
+        mask = np.ascontiguousarray(p["mask"], dtype=np.uint8)
+        dwm = _dev("wm", what, mask.nbytes, mask.shape[1], mask)
+        code = lib.mipx_op_text_watermark(din.ptr, dwm.ptr, dout.ptr, n, w, h, b, mask.shape[1], mask.shape[0],
+                                          p["margin"], p["opacity"], (C.c_int32 * 3)(*p["colour"]), None)
     elif name == "affine":
         code = lib.mipx_op_affine(din.ptr, dout.ptr, n, w, h, b, p["xscale"], p["yscale"], p.get("extend", 1), None)
     elif name == "zoom":

@@ -3,7 +3,7 @@
 Reference: image.go (OperationsMap 15-32, Process 81-113, Resize 115, Fit 139,
 calculateDestinationFitDimension 190, Enlarge 202, Extract 213, Crop 226,
 SmartCrop 236, Rotate 247, Flip 267, Flop 273, Thumbnail 279, Zoom 286,
-WatermarkImage 343, GaussianBlur 372, Pipeline 379), options.go (ImageOptions
+Watermark 322, WatermarkImage 343, GaussianBlur 372, Pipeline 379), options.go (ImageOptions
 11-52, BimgOptions 128-172) and params.go (buildParamsFromQuery 354-366,
 parseInt 376-390, parseExtendMode 421-437, parseGravity 439-453).
 
@@ -28,7 +28,8 @@ from typing import Any, Callable, Dict, List, Optional
 import numpy as np
 
 from . import _abi, codec
-from .engine import Engine, fit_dimension, make_input, make_opts, plan_chain, plan_make
+from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_textmark, plan_chain, plan_make,
+                     plan_textmark_geometry)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -58,6 +59,7 @@ class IsDefinedField:
     embed: bool = False
     no_crop: bool = False
     no_rotation: bool = False
+    no_replicate: bool = False
 
 
 @dataclass
@@ -77,6 +79,11 @@ class ImageOptions:
     embed: bool = False
     no_crop: bool = False
     no_rotation: bool = False
+    no_replicate: bool = False   # text watermark: bimg Watermark.NoReplicate
+    margin: int = 0          # text watermark: gap between repeats (0 = the text width)
+    dpi: int = 0             # text watermark: render resolution (0 = 150)
+    text_width: int = 0      # text watermark: wrap width (0 = image width / 6)
+    font: str = ""           # text watermark: pango font description ("" = "sans 10")
     opacity: float = 0.0
     sigma: float = 0.0
     min_ampl: float = 0.0
@@ -84,12 +91,12 @@ class ImageOptions:
     type: str = ""
     aspect_ratio: str = ""
     background: List[int] = field(default_factory=list)
-    color: List[int] = field(default_factory=list)   # text watermark colour (not a pixel-engine op)
+    color: List[int] = field(default_factory=list)   # text watermark colour
     extend: int = 1          # bimg.ExtendCopy default (params.go:342, 356)
     colorspace: int = 0      # bimg.Interpretation (params.go:260, parseColorspace 392)
     quality: int = 0
     compression: int = 0
-    text: str = ""           # Watermark (text): pango rendering, not a pixel-engine op
+    text: str = ""           # Watermark (text): the host renders it, the engine blends the mask
     gravity: int = 0
     operations: List[Dict[str, Any]] = field(default_factory=list)
     is_defined: IsDefinedField = field(default_factory=IsDefinedField)
@@ -298,11 +305,11 @@ def coerce_type_string(p):
 
 _INT_PARAMS = {"width": "width", "height": "height", "areawidth": "area_width", "areaheight": "area_height",
                "rotate": "rotate", "top": "top", "left": "left", "factor": "factor", "quality": "quality",
-               "compression": "compression"}
+               "compression": "compression", "margin": "margin", "dpi": "dpi", "textwidth": "text_width"}
 _FLOAT_PARAMS = {"sigma": "sigma", "minampl": "min_ampl", "opacity": "opacity"}
 _BOOL_PARAMS = {"flip": "flip", "flop": "flop", "force": "force", "embed": "embed", "nocrop": "no_crop",
-                "norotation": "no_rotation"}
-_STR_PARAMS = {"type": "type", "aspectratio": "aspect_ratio", "image": "image", "text": "text"}
+                "norotation": "no_rotation", "noreplicate": "no_replicate"}
+_STR_PARAMS = {"type": "type", "aspectratio": "aspect_ratio", "image": "image", "text": "text", "font": "font"}
 
 
 def _coerce(o: ImageOptions, k: str, v) -> None:
@@ -439,7 +446,41 @@ def _run(plan, px, wm):
         raise ImaginaryError(f"image processing error: {e}", 500) from e
 
 
-def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None):
+@dataclass
+class TextMark:
+    """A text watermark request (bimg.Watermark as image.go:327-338 fills it) plus the
+    host's renderer: render(text, font, width, dpi) -> 2-D uint8 coverage mask, what
+    vips_text returns."""
+    render: Callable[[str, str, int, int], np.ndarray]
+    text: str
+    font: str = ""
+    width: int = 0
+    dpi: int = 0
+    margin: int = 0
+    opacity: float = 0.0
+    colour: tuple = (0, 0, 0)
+    no_replicate: bool = False
+
+
+def _add_textmark(plan, t: TextMark) -> np.ndarray:
+    """bimg watermarkImageWithText on a finished plan: its defaults from the image at the
+    insertion point, the host render, then the TEXTMARK step.  Returns the mask, which
+    travels as the request's watermark image."""
+    if t.no_replicate:   # the planner refuses it too; no need to render first
+        raise EngineUnsupported("text watermark with noreplicate is not implemented by the engine")
+    w, _, _ = plan_textmark_geometry(plan)
+    width = t.width or w // 6
+    dpi = t.dpi or 150
+    margin = t.margin or width
+    mask = np.ascontiguousarray(t.render(t.text, t.font or "sans 10", width, dpi), dtype=np.uint8)
+    if mask.ndim != 2 or mask.size == 0:
+        raise ImaginaryError("text watermark: the renderer returned no mask", 500)
+    plan_add_textmark(plan, mask.shape[1], mask.shape[0], margin, t.opacity, t.colour)
+    return mask[:, :, None]
+
+
+def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
+            text: Optional[TextMark] = None):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -448,9 +489,11 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     without one, a plan that asks for load_shrink > 1 is rejected.
     With `chain` (a list), a Decoded input is planned but not run: (plan, pixels,
     watermark) is appended and placeholder pixels of the output shape returned
-    (Pipeline fuses the stages into one device-resident plan)."""
+    (Pipeline fuses the stages into one device-resident plan).
+    With `text`, the plan gets a text watermark step and the rendered mask takes the
+    watermark slot."""
     if isinstance(img, (bytes, bytearray, memoryview)):
-        return process_bytes(bytes(img), opts, wm)
+        return process_bytes(bytes(img), opts, wm, text)
     opts = {k: v for k, v in opts.items() if k not in _ENCODE_ONLY}
     px = img.pixels if img.pixels.ndim == 3 else img.pixels[:, :, None]
     inp = make_input(img.w, img.h, px.shape[2], img.type, img.orientation)
@@ -468,17 +511,19 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
             plan = plan_make(make_opts(**opts), inp)
         elif img.header_w and (img.header_w, img.header_h) != (px.shape[1], px.shape[0]):
             raise ImaginaryError("decoded size does not match the header", 500)
+        if text is not None:
+            wm = _add_textmark(plan, text)
         if chain is not None:
             chain.append((plan, px, wm))
             return _placeholder(plan.out_h, plan.out_w, plan.out_bands)
-        return engine().process(plan, px, wm)
+        return _run(plan, px, wm)
     except _abi.MipxError as e:
         if e.code == _abi.MIPX_EUNSUPPORTED:
             raise EngineUnsupported(str(e)) from e
         raise ImaginaryError(f"image processing error: {e}", 500) from e
 
 
-def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None) -> Image:
+def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112)."""
@@ -510,12 +555,12 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None) -> Image:
         raise ImaginaryError(f"image processing error: {e}", 500) from e
     rotates = any(step[0] in ("rot", "flip") for step in plan.describe())
     if plan.load_shrink > 1 and itype == "jpeg" and rotates and not opts.get("no_auto_rotate"):
-        px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px)
+        px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text)
     elif plan.load_shrink > 1:  # process() re-plans on the codec-shrunk size
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
-        px = process(src, opts, wm=wm_px, redecode=redecode)
+        px = process(src, opts, wm=wm_px, redecode=redecode, text=text)
     else:
-        px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px)
+        px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text)
     t = out_type or (hdr.type if hdr.type in ("jpeg", "png", "webp", "gif", "tiff") else "png")
     try:
         body = codec.encode(px, t, quality or None, compression)
@@ -541,7 +586,8 @@ def _drop_leading_steps(plan, k: int, w: int, h: int):
     return rest
 
 
-def _rotate_reencode_shrink_on_load(buf: bytes, hdr, itype: str, opts: Dict[str, Any], wm_px):
+def _rotate_reencode_shrink_on_load(buf: bytes, hdr, itype: str, opts: Dict[str, Any], wm_px,
+                                    text: Optional[TextMark] = None):
     """bimg 1.1.9 resizer() for a JPEG that rotates or flips (EXIF orientation or an
     explicit rotate / flip / flop) and then shrinks on load (image.go:96 -> bimg
     resizer.go): rotateAndFlipImage runs on the FULL-size decode, the rotated image is
@@ -575,6 +621,8 @@ def _rotate_reencode_shrink_on_load(buf: bytes, hdr, itype: str, opts: Dict[str,
         swap = upright.shape[:2] != full.shape[:2]
         inp.decoded_w, inp.decoded_h = (px.shape[0], px.shape[1]) if swap else (px.shape[1], px.shape[0])
         plan = plan_make(make_opts(**opts), inp)
+        if text is not None:
+            wm_px = _add_textmark(plan, text)
     except _abi.MipxError as e:
         if e.code == _abi.MIPX_EUNSUPPORTED:
             raise EngineUnsupported(str(e)) from e
@@ -681,11 +729,18 @@ def Convert(img, o: ImageOptions, **kw):
     return process(img, bimg_options(o), **kw)
 
 
-def Watermark(img, o: ImageOptions, **kw):
-    """image.go:322-341: text watermark (pango rendering) stays with libvips."""
+def Watermark(img, o: ImageOptions, render: Optional[Callable] = None, **kw):
+    """image.go:322-341.  Glyph rendering is host work, like the codec: `render(text, font,
+    width, dpi)` returns the 2-D uint8 mask vips_text would (codec.render_text is a
+    stand-in) and the engine tiles and blends it (MIPX_OP_TEXTMARK).  Without a renderer
+    the operation stays with libvips."""
     if o.text == "":
         raise ImaginaryError("Missing required param: text")
-    raise EngineUnsupported("text watermark is rendered by libvips, not the pixel engine")
+    if render is None:
+        raise EngineUnsupported("text watermark is rendered by libvips, not the pixel engine")
+    colour = tuple(o.color[:3]) if len(o.color) > 2 else (0, 0, 0)   # image.go:336-338
+    text = TextMark(render, o.text, o.font, o.text_width, o.dpi, o.margin, float(o.opacity), colour, o.no_replicate)
+    return process(img, bimg_options(o), text=text, **kw)
 
 
 def Info(buf: bytes, o: ImageOptions, **kw) -> Image:
@@ -757,8 +812,10 @@ OperationsMap: Dict[str, Callable] = {
 
 
 def _stage_kw(fn, kw):
-    """The caller's watermark pixels belong to watermarkImage stages only."""
-    return kw if fn is WatermarkImage else {k: v for k, v in kw.items() if k != "wm"}
+    """The caller's watermark pixels belong to watermarkImage stages only, the text
+    renderer to watermark stages only."""
+    keep = {WatermarkImage: "wm", Watermark: "render"}.get(fn)
+    return {k: v for k, v in kw.items() if k not in ("wm", "render") or k == keep}
 
 
 def Pipeline(img, o: ImageOptions, **kw):

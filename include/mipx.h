@@ -24,7 +24,7 @@
  *    again, or call mipx_cancel before freeing the buffer.
  *  - Plans are validated before use: every step's out_w/out_h/out_bands must be
  *    what its op makes from the previous step's geometry (MIPX_EINVAL otherwise),
- *    and a watermark image must have the watermark step's geometry.
+ *    and a watermark image (or rendered text mask) must have the watermark step's geometry.
  *  - All mipx_op_* / mipx_execute_dev entry points take DEVICE pointers to a
  *    batch of n equally sized images packed back to back, and a hipStream_t
  *    passed as void* (NULL = the device's default engine stream).  They only
@@ -123,7 +123,10 @@ enum {
     MIPX_OP_AFFINE,      /* d[0] = xscale, d[1] = yscale, a[0] = extend; bicubic  (vips_affine) */
     MIPX_OP_ZOOM,        /* a[0] = xfac, a[1] = yfac                         (vips_zoom) */
     MIPX_OP_FLATTEN,     /* a[0..2] = background rgb                         (vips_flatten) */
-    MIPX_OP_BW           /* sRGB -> B_W                                      (vips_colourspace) */
+    MIPX_OP_BW,          /* sRGB -> B_W                                      (vips_colourspace) */
+    MIPX_OP_TEXTMARK     /* a[0..1] = mask w, h; a[2] = margin; a[3..5] = colour; d[0] = opacity after
+                            defaulting; out_bands = 3; the rendered text mask travels as the request's
+                            watermark image (a[0] x a[1] x 1)              (bimg vips_watermark) */
 };
 
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
@@ -177,10 +180,26 @@ int mipx_plan_make(const mipx_opts *opts, const mipx_input *in, mipx_plan *plan)
  * a pipeline's stages (stage k planned on stage k-1's output, decoded intermediates)
  * into one plan, so the request path runs the chain with one upload, device-resident
  * intermediates and one download.  Stage k > 0 must take stage k-1's output geometry
- * and have load_shrink 1; at most one stage may carry a watermark step.
+ * and have load_shrink 1; at most one stage may carry a watermark step (WATERMARK or
+ * TEXTMARK: a request has one watermark image).
  * MIPX_EUNSUPPORTED when the chain exceeds MIPX_MAX_STEPS or has two watermark stages
  * (the caller then runs the stages one by one). */
 int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out);
+/* Text watermark (imaginary image.go:322-341 Watermark, bimg watermarkImageWithText): the
+ * host renders the text (vips_text) and the engine tiles and blends the 1-band mask
+ * (MIPX_OP_TEXTMARK).  The step sits after the blur and before the watermark image,
+ * flatten and B_W steps of a mipx_plan_make plan.  Both calls work without a GPU.
+ * mipx_plan_textmark_geometry: the image at that insertion point, so the host can apply
+ * bimg's text width default (floor(w / 6)) before it renders.
+ * mipx_plan_add_textmark: inserts the step (opacity 0 -> 0.25, above 1 -> 1, as bimg).
+ * MIPX_EINVAL for a non-positive mask size, a negative margin, a colour outside 0..255 or a
+ * full plan; MIPX_EUNSUPPORTED (the caller falls back to bimg) when no_replicate is set,
+ * when the image there has 2 or 4 bands (libvips refuses the 3-band colour against it),
+ * when the plan already has a WATERMARK or TEXTMARK step (one watermark slot per request),
+ * or when a 1-band image (which leaves the step with 3 bands) has steps after it. */
+int mipx_plan_textmark_geometry(const mipx_plan *plan, int32_t *w, int32_t *h, int32_t *bands);
+int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t mask_h, int32_t margin, float opacity,
+                           const int32_t *colour3, int32_t no_replicate);
 /* imaginary image.go:190 calculateDestinationFitDimension */
 int mipx_fit_dimension(int32_t image_w, int32_t image_h, int32_t fit_w, int32_t fit_h,
                        int32_t *out_w, int32_t *out_h);
@@ -241,6 +260,13 @@ int mipx_op_gaussblur(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w,
 int mipx_op_watermark(const uint8_t *d_base, const uint8_t *d_wm, uint8_t *d_out, int32_t n,
                       int32_t w, int32_t h, int32_t bands, int32_t wm_w, int32_t wm_h,
                       int32_t wm_bands, int32_t left, int32_t top, float opacity, void *stream);
+/* The text watermark after rendering: d_mask is the rendered text, mask_w x mask_h x 1;
+ * the output has 3 bands (a 1-band image is up-banded against the colour).
+ * MIPX_EINVAL, before any HIP call, for NULL pointers, n <= 0, non-positive sizes, a
+ * negative margin or a colour outside 0..255; MIPX_EUNSUPPORTED for 2 or 4 bands. */
+int mipx_op_text_watermark(const uint8_t *d_in, const uint8_t *d_mask, uint8_t *d_out, int32_t n,
+                           int32_t w, int32_t h, int32_t bands, int32_t mask_w, int32_t mask_h,
+                           int32_t margin, float opacity, const int32_t *colour3, void *stream);
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                    int32_t bands, double xscale, double yscale, int32_t extend, void *stream);
 int mipx_op_zoom(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,

@@ -3,7 +3,8 @@
 rocprofv3 passes see that kernel alone.
 
     python scripts/op_bench.py reducev --w 1024 --h 1024 --b 4 --n 512 --s 1.3333333333333333
-    ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom
+    python scripts/op_bench.py textmark --w 3840 --h 2160 --b 3 --n 64
+    ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark
 """
 import argparse
 import ctypes as C
@@ -35,6 +36,10 @@ def main():
     ap.add_argument("--ow", type=int, default=0)
     ap.add_argument("--oh", type=int, default=0)
     ap.add_argument("--extend", type=int, default=1)
+    ap.add_argument("--mw", type=int, default=0, help="textmark / watermark: mask or watermark width (0 = w / 6)")
+    ap.add_argument("--mh", type=int, default=0, help="textmark / watermark: mask or watermark height (0 = mw / 5)")
+    ap.add_argument("--margin", type=int, default=-1, help="textmark: margin (-1 = the mask width, bimg's default)")
+    ap.add_argument("--opacity", type=float, default=0.25)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -63,8 +68,22 @@ def main():
         ow, oh = a.ow or w, a.oh or h
     else:
         ow, oh = w, h
+    ob = b
+    mw = a.mw or max(1, w // 6)
+    mh = a.mh or max(1, mw // 5)
+    if a.op == "textmark":      # a text-like mask: a third of it covered, the rest 0
+        ob = 3
+        g = torch.Generator(device="cpu").manual_seed(1)
+        m = torch.randint(0, 256, (mh * mw,), dtype=torch.uint8, generator=g)
+        m[torch.rand(mh * mw, generator=g) > 0.35] = 0
+        mask = m.to(dev)
+    elif a.op == "watermark":   # an RGBA watermark image at (100, 100)
+        ob = b if b in (2, 4) else b + 1
+        mask = torch.randint(0, 256, (mh * mw * 4,), dtype=torch.uint8, device=dev)
+    margin = mw if a.margin < 0 else a.margin
+    colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * w * h * b,), dtype=torch.uint8, device=dev)
-    y = torch.empty((n * ow * oh * b,), dtype=torch.uint8, device=dev)
+    y = torch.empty((n * ow * oh * ob,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream(dev)
     sp = C.c_void_p(st.cuda_stream)
@@ -94,6 +113,10 @@ def main():
             return lib.mipx_op_affine(X, Y, n, w, h, b, a.s, s2, a.extend, sp)
         if a.op == "zoom":
             return lib.mipx_op_zoom(X, Y, n, w, h, b, int(a.s), int(s2), sp)
+        if a.op == "textmark":
+            return lib.mipx_op_text_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, margin, a.opacity, colour, sp)
+        if a.op == "watermark":
+            return lib.mipx_op_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, 4, 100, 100, a.opacity, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -121,8 +144,8 @@ def main():
             groups.append(e0.elapsed_time(e1) / a.iters)
         return sorted(groups)[len(groups) // 2]
 
-    alg = n * (w * h * b + ow * oh * b)
-    line = {"op": a.op, "w": w, "h": h, "b": b, "n": n, "s": a.s, "s2": s2, "out": [ow, oh],
+    alg = n * (w * h * b + ow * oh * ob)   # bytes = input + output
+    line = {"op": a.op, "w": w, "h": h, "b": b, "n": n, "s": a.s, "s2": s2, "out": [ow, oh, ob],
             "sampling": ["corner", "centre"][lib.mipx_reduce_sampling()]}
     if not a.ab:
         ms = measure()
