@@ -657,70 +657,48 @@ int enlm_ix(int o, double s, int *phase) {
 
 // Per-axis records of k_enlm, output positions 0 .. cap - 1 at scale s: {first window
 // pixel + 2 (af_ix), the phase's tap sum, taps 0 1, taps 2 3 as int16 pairs}.  A record
-// depends on (o, s) only, so one table per (device, scale) serves every size; grown by
-// doubling (a replaced table stays allocated: kernels in flight may read it).  Dropped
-// when the engine's device tables are (device_tables_generation).
-struct EmAxis {
-    std::vector<int> host;  // [cap][kEmRec]
-    const int4 *dev;
-    unsigned gen;
-};
+// depends on (o, s) only, so one table per scale serves every size; grown by doubling.
+// The host copy stays here (planning reads it); the device copies are the engine's
+// growable device table (device_enlm_axis), freed with the others at shutdown.
 std::mutex g_em_mu;
-std::map<std::pair<int, double>, EmAxis> &em_axes() {
-    static auto *m = new std::map<std::pair<int, double>, EmAxis>();
+std::map<double, std::vector<int>> &em_axes() {  // per scale: [cap][kEmRec]
+    static auto *m = new std::map<double, std::vector<int>>();
     return *m;
 }
-std::vector<std::pair<int, int4 *>> &em_retired() {  // (device, table)
-    static auto *v = new std::vector<std::pair<int, int4 *>>();
-    return *v;
-}
 
-const EmAxis *em_axis_locked(int dev, double s, int n) {
-    const unsigned gen = device_tables_generation();
-    auto &m = em_axes();
-    auto it = m.find({dev, s});
-    if (it != m.end() && it->second.gen == gen && static_cast<int>(it->second.host.size() / kEmRec) >= n) return &it->second;
-    int cap = 1024;
-    while (cap < n) cap *= 2;
-    int tab[(kTransformScale + 1) * 4];
-    bicubic_table(tab);
-    EmAxis ax;
-    ax.host.resize(static_cast<size_t>(cap) * kEmRec);
-    for (int o = 0; o < cap; ++o) {
-        int ph = 0;
-        const int p = enlm_ix(o, s, &ph);
-        const int *c = tab + 4 * ph;
-        int *r = ax.host.data() + kEmRec * static_cast<size_t>(o);
-        const int sum = c[0] + c[1] + c[2] + c[3];
-        r[0] = p;
-        r[1] = sum;
-        r[2] = static_cast<int>((static_cast<uint32_t>(c[0]) & 0xffffu) | (static_cast<uint32_t>(c[1]) << 16));
-        r[3] = static_cast<int>((static_cast<uint32_t>(c[2]) & 0xffffu) | (static_cast<uint32_t>(c[3]) << 16));
-        // as a row: {pos, tap sum, Ch + 64 (u8 x 4), Cl (u8 x 4)} (C = 64 Ch + Cl)
-        uint32_t hi = 0, lo = 0;
-        for (int k = 0; k < 4; ++k) {
-            hi |= static_cast<uint32_t>((c[k] >> 6) + 64) << (8 * k);
-            lo |= static_cast<uint32_t>(c[k] & 63) << (8 * k);
+// the records of scale s over at least n positions; *dev = the current device's copy
+const std::vector<int> *em_axis_locked(double s, int n, const int4 **dev) {
+    std::vector<int> &host = em_axes()[s];
+    if (static_cast<int>(host.size() / kEmRec) < n) {
+        int cap = 1024;
+        while (cap < n) cap *= 2;
+        int tab[(kTransformScale + 1) * 4];
+        bicubic_table(tab);
+        host.resize(static_cast<size_t>(cap) * kEmRec);
+        for (int o = 0; o < cap; ++o) {
+            int ph = 0;
+            const int p = enlm_ix(o, s, &ph);
+            const int *c = tab + 4 * ph;
+            int *r = host.data() + kEmRec * static_cast<size_t>(o);
+            const int sum = c[0] + c[1] + c[2] + c[3];
+            r[0] = p;
+            r[1] = sum;
+            r[2] = static_cast<int>((static_cast<uint32_t>(c[0]) & 0xffffu) | (static_cast<uint32_t>(c[1]) << 16));
+            r[3] = static_cast<int>((static_cast<uint32_t>(c[2]) & 0xffffu) | (static_cast<uint32_t>(c[3]) << 16));
+            // as a row: {pos, tap sum, Ch + 64 (u8 x 4), Cl (u8 x 4)} (C = 64 Ch + Cl)
+            uint32_t hi = 0, lo = 0;
+            for (int k = 0; k < 4; ++k) {
+                hi |= static_cast<uint32_t>((c[k] >> 6) + 64) << (8 * k);
+                lo |= static_cast<uint32_t>(c[k] & 63) << (8 * k);
+            }
+            r[4] = p;
+            r[5] = sum;
+            r[6] = static_cast<int>(hi);
+            r[7] = static_cast<int>(lo);
         }
-        r[4] = p;
-        r[5] = sum;
-        r[6] = static_cast<int>(hi);
-        r[7] = static_cast<int>(lo);
     }
-    int4 *d = nullptr;
-    if (hipMalloc(&d, ax.host.size() * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, ax.host.data(), ax.host.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return nullptr;
-    }
-    if (it != m.end()) {
-        if (it->second.gen == gen) em_retired().emplace_back(dev, const_cast<int4 *>(it->second.dev));  // may be in flight
-        else (void)hipFree(const_cast<int4 *>(it->second.dev));  // an older generation's: unused (shutdown drained)
-    }
-    ax.dev = d;
-    ax.gen = gen;
-    m[{dev, s}] = std::move(ax);
-    return &m[{dev, s}];
+    *dev = static_cast<const int4 *>(device_enlm_axis(s, host, kEmRec, n));
+    return *dev ? &host : nullptr;
 }
 
 // k_enlm's geometry, or false when the scale is outside its tiles: every unit's taps within
@@ -787,12 +765,12 @@ bool enlm_plan(int n, int w, int h, int b, int ow, int oh, double xs, double ys,
     }
     if (plans->size() > 1024) plans->clear();
     EmPlan pl{false, 0, 4, EnlmArgs{}, gen};
-    const EmAxis *cx = em_axis_locked(dev, xs, ow);
-    const int4 *cols = cx ? cx->dev : nullptr;
-    const std::vector<int> xh = cx ? cx->host : std::vector<int>();
-    const EmAxis *cy = em_axis_locked(dev, ys, oh);
-    if (!cols || !cy) return false;
-    const int *px = xh.data(), *py = cy->host.data();
+    const int4 *cols = nullptr, *rows = nullptr;
+    const std::vector<int> *cx = em_axis_locked(xs, ow, &cols);
+    const std::vector<int> xh = cx ? *cx : std::vector<int>();  // the next call may grow it (xs == ys)
+    const std::vector<int> *cy = em_axis_locked(ys, oh, &rows);
+    if (!cx || !cy) return false;
+    const int *px = xh.data(), *py = cy->data();
     const int rowb = ow * b;
     int nk = 1, iwb = 0, nu = 8;
     const long long waves8 = static_cast<long long>((rowb + 127) / 128) * ((oh + 127) / 128) * n;
@@ -839,7 +817,7 @@ bool enlm_plan(int n, int w, int h, int b, int ow, int oh, double xs, double ys,
     }
     if (ok) {
         pl.g.cols = cols;
-        pl.g.rows = cy->dev;
+        pl.g.rows = rows;
         pl.g.groups = groups;
         pl.g.bands = bands;
         pl.g.br = br;
@@ -859,25 +837,6 @@ bool enlm_plan(int n, int w, int h, int b, int ow, int oh, double xs, double ys,
 }
 
 }  // namespace
-
-// Called by free_device_tables (mipx_shutdown, after every queue drained): the axis
-// tables, the retired ones and the cached plans that point at them.
-void free_enlm_tables() {
-    std::lock_guard<std::mutex> lk(g_em_mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &kv : em_axes()) {
-        (void)hipSetDevice(kv.first.first);
-        (void)hipFree(const_cast<int4 *>(kv.second.dev));
-    }
-    em_axes().clear();
-    for (auto &r : em_retired()) {
-        (void)hipSetDevice(r.first);
-        (void)hipFree(r.second);
-    }
-    em_retired().clear();
-    (void)hipSetDevice(cur);
-}
 
 int affine_launch(const u8 *in, u8 *out, int n, int w, int h, int b, double xs, double ys, int extend,
                   hipStream_t st) {

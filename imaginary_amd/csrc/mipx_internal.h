@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "mipx.h"
+#include "mipx_tables.h"  // the libvips table maths, table layouts and host builders (no HIP)
 
 namespace mipx {
 
@@ -49,7 +50,6 @@ class SamplingScope {
 };
 // requests submitted through mipx_submit and not yet retired (mipx_runtime.cpp)
 long long requests_in_flight();
-inline double reduce_x_host(int o, double s, bool centre) { return centre ? (o + 0.5) * s - 0.5 : o * s; }
 
 // ---- device properties, cached per device (mipx_tuning.cpp) --------------------
 // compute units of the current device (256 on an MI355X in SPX mode; fewer per
@@ -64,27 +64,6 @@ int occupancy_per_cu(const void *fn, int threads, size_t lds, int fallback);
 // Do direct-to-LDS dword buffer loads honour byte offsets that are not multiples of 4?
 bool lds_dma_unaligned_ok();
 
-// ---- libvips resample constants (resample/templates.h, [U]) ----------------
-constexpr int kTransformScale = 128;  // VIPS_TRANSFORM_SCALE: 129 sub-pixel phases
-constexpr int kInterpShift = 12;      // VIPS_INTERPOLATE_SHIFT
-constexpr int kInterpScale = 1 << kInterpShift;
-
-// Lanczos3 reduce geometry (libvips reduceh.cpp / reducev.cpp).
-int reduce_points(double shrink);                      // 2 * rint(3 * shrink) + 1
-void reduce_table(double shrink, std::vector<int> &t); // 129 x n truncated 12-bit taps
-int out_size_reduce(int in, double shrink);            // VIPS_ROUND(in / shrink)
-int out_size_shrink(int in, int shrink);               // VIPS_ROUND(in / shrink)
-
-// Integer gaussmat (libvips create/gaussmat.c): returns width, fills mask/scale.
-int gaussmat(double sigma, double min_ampl, std::vector<int> &mask, int &scale);
-
-// Colour LUTs for the smartcrop scorer (libvips colour/*.c, [U]).
-constexpr int kQuantElements = 100000;
-const float *v2y8_table();    // 256 entries: sRGB 8-bit -> linear
-const float *cbrt_table();    // kQuantElements entries: Lab f(t)
-const float *y2v8_table();    // 257 entries: linear Y x 255 -> sRGB 8-bit (B_W)
-void bicubic_table(int *t);   // 129 x 4 bicubic taps (vips_affine)
-
 // vips_resize() downsize schedule used by the smartcrop scorer.
 struct ResizeSchedule {
     int shrink_h = 1, shrink_v = 1;    // integer box shrink
@@ -94,29 +73,25 @@ struct ResizeSchedule {
 };
 int resize_schedule(int w, int h, double hscale, double vscale, ResizeSchedule &s);
 
-// ---- device-side cached tables ----------------------------------------------
+// ---- device-side cached tables (mipx_device_tables.cpp) -----------------------
+// Each fetcher returns the table on the current device, built (mipx_tables.h) and uploaded on
+// first use; nullptr when there is no such table or the device refused it.
 // float copy of reduce_table(shrink) resident on the current device.
 const float *device_reduce_table(double shrink, int *n_taps);
 // the same taps packed as int16 pairs: [129][2 alignments][*tpa] (k_rstrip)
 const uint32_t *device_reduce_pairs(double shrink, int *n_taps, int *tpa);
-constexpr int kHmTabW = 64;     // k_hmfma i8 tap rows: bytes per (phase, hi / lo) row (16.5 KB: L1-resident)
-constexpr int kHmTabPad = 16;   // zero bytes in front of tap 0 (taps <= 16; windows clamped to [-16, 16])
-constexpr int kRsTabPad = 128;  // k_rmf4 stride-B tap rows: zero bytes in front of tap 0
-constexpr int kRsTabW = 272;    // bytes per (phase, hi / lo) row: pad + 2 K steps + a fragment (70 KB per table)
 const signed char *device_reduce_i8(double shrink, int *n_taps, const int **sums);
 const signed char *device_reduce_i8s(double shrink, int bands, int *n_taps);  // taps at a byte stride of bands
 // the same with the COPY edge folded in: [2 sides][taps - 1][129][hi, lo][kRsTabW] (k_rcol)
 const signed char *device_reduce_i8s_fold(double shrink, int bands, int *n_taps);
 // k_rcol's vertical plan (per output row: K-placed split taps + seed; per 16-row group:
 // first / end input rows) over at least `rows` op-output rows; *cap_rows = rows it holds
-constexpr int kRcolPlanRow = 144;
 const uint8_t *device_rcol_vplan(double shrink, bool centre, int rows, int *cap_rows);
 // k_rcol's horizontal operands of one window geometry, built on the host (r06): per 64-pixel
 // strip, per 16-byte output unit u < 4 bands, per lane: per K step the hi / lo tap fragments
 // (COPY edge folded, odd K blocks' halves swapped), then the four per-byte seeds,
 // kRcolHopRec(nks) bytes; then per (strip, unit) the K origin (int).  The specialised k_rcol
 // builds load these instead of computing the positions in the block's set-up.
-constexpr int kRcolHopRec(int nks) { return 32 * nks + 16; }
 const uint8_t *device_rcol_hops(double hs, int bands, bool centre, int ox0, int ow, int w, int k4, int nks, int *strips);
 // k_bmf's i8 MFMA operands for a blur mask (cached per device): [nks][64][16]
 // horizontal taps at byte stride `bands` shifted by delta, then [64][16] vertical taps
@@ -127,12 +102,14 @@ const int *device_bicubic_table();     // 129 x 4
 const float *device_gauss_table(double sigma, double min_ampl, int *n_taps, int *scale);
 // `bytes` of host data on the current device, cached by contents (small constant tables)
 const void *device_blob(const void *data, size_t bytes);
+// k_enlm's per-axis records (host: [rows][rec_ints] ints, built and kept by k_affine.hip) on the
+// current device, holding at least min_rows rows; grown like the vertical plan
+const void *device_enlm_axis(double scale, const std::vector<int> &host, int rec_ints, int min_rows);
+// frees every table above on every device (mipx_shutdown, after every queue drained)
 void free_device_tables();
-// bumped by free_device_tables: a launcher that caches a table pointer outside the maps
-// above keeps the generation it was made in and refetches when it changed
+// bumped by free_device_tables: a launcher that caches a table pointer of its own
+// keeps the generation it was made in and refetches when it changed
 unsigned device_tables_generation();
-// free_device_tables also frees every table k_enlm keeps per (device, scale) (k_affine.hip)
-void free_enlm_tables();
 
 // ---- generic separable passes (k_sep.hip) -----------------------------------
 enum { kSepReduce = 0, kSepConv = 1 };

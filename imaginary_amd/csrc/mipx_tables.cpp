@@ -1,0 +1,352 @@
+// mipx_tables.cpp — host builders of the device-resident tables: the libvips taps laid out
+// as each kernel reads them (per-lane MFMA operands, K-index permutations, folded edges,
+// seeds).  No HIP call in this file; mipx_device_tables.cpp uploads and caches the results.
+// Built without FP contraction, as the oracle (positions are separately rounded doubles).
+#include <algorithm>
+#include <cstring>
+
+#include "mipx_tables.h"
+
+namespace mipx {
+namespace {
+
+template <class T>
+std::vector<uint8_t> as_bytes(const std::vector<T> &v) {
+    std::vector<uint8_t> b(v.size() * sizeof(T));
+    if (!b.empty()) std::memcpy(b.data(), v.data(), b.size());
+    return b;
+}
+
+// a 12-bit tap as two i8 MFMA operands: c = 64 hi + lo, hi = c >> 6 (signed), lo = c & 63
+inline void split_tap(int c, uint8_t *hi, uint8_t *lo) {
+    *hi = static_cast<uint8_t>(static_cast<signed char>(c >> 6));
+    *lo = static_cast<uint8_t>(c & 63);
+}
+
+// the first input pixel of output o's taps (pad = taps / 2 - 1) and its phase
+inline int reduce_pos(int o, double shrink, bool centre, int pad, int *phase) {
+    const double X = reduce_x_host(o, shrink, centre);
+    if (phase) *phase = ((static_cast<int>(X * 256.0) & 255) + 1) >> 1;
+    return static_cast<int>(X) - pad;
+}
+
+// libvips' COPY edge folded into a tap row c[0 .. n).  Left, amount a: the first tap pixel is
+// -a, so taps 0..a land on pixel 0 (their sum at tap a, zeros before).  Right, amount a: the
+// last tap pixel is w - 1 + a, so taps n-1-a .. n-1 land on pixel w - 1 (their sum at tap
+// n-1-a, zeros after).
+void fold_left(const int *c, int n, int a, int *f) {
+    int sum = 0;
+    for (int k = 0; k < n; ++k) {
+        if (k <= a) sum += c[k];
+        f[k] = k < a ? 0 : k == a ? sum : c[k];
+    }
+}
+void fold_right(const int *c, int n, int a, int *f) {
+    const int e = n - 1 - a;
+    int sum = 0;
+    for (int k = e; k < n; ++k) sum += c[k];
+    for (int k = 0; k < n; ++k) f[k] = k > e ? 0 : k == e ? sum : c[k];
+}
+
+}  // namespace
+
+// float copy of reduce_table(shrink): [129 phases][taps]
+HostTable build_reduce_table(double shrink) {
+    std::vector<int> t;
+    reduce_table(shrink, t);
+    HostTable r;
+    r.bytes = as_bytes(std::vector<float>(t.begin(), t.end()));
+    r.meta[0] = reduce_points(shrink);
+    return r;
+}
+
+// The same taps as int16 pairs for v_dot2: [129 phases][2 alignments][tpa]
+// words, tpa = taps / 2 + 1; alignment 0 = (c[2m], c[2m+1]), alignment 1 =
+// (c[2m-1], c[2m]) (taps outside [0, taps) are 0).  k_rstrip reads them directly.
+HostTable build_reduce_pairs(double shrink) {
+    const int n = reduce_points(shrink), w = n / 2 + 1;
+    std::vector<int> t;
+    reduce_table(shrink, t);
+    std::vector<uint32_t> h(static_cast<size_t>(kTransformScale + 1) * 2 * w);
+    auto tap = [&](int ph, int i) -> uint32_t {
+        return (i < 0 || i >= n) ? 0u : static_cast<uint32_t>(t[static_cast<size_t>(ph) * n + i]) & 0xffffu;
+    };
+    for (int ph = 0; ph <= kTransformScale; ++ph)
+        for (int al = 0; al < 2; ++al)
+            for (int m = 0; m < w; ++m)
+                h[(static_cast<size_t>(ph) * 2 + al) * w + m] = tap(ph, 2 * m - al) | (tap(ph, 2 * m + 1 - al) << 16);
+    HostTable r;
+    r.bytes = as_bytes(h);
+    r.meta[0] = n;
+    r.meta[1] = w;
+    return r;
+}
+
+// The same taps split for the i8 MFMA horizontal reduce (k_hmfma): per phase two
+// rows of kHmTabW bytes, hi = c >> 6 and lo = c & 63 (c = 64 hi + lo, both fit
+// i8), tap i at byte kHmTabPad + i, zeros around; after the 129 x 2 rows, 129
+// ints holding each phase's tap sum (the bias of the pixel - 128 offset).
+HostTable build_reduce_i8(double shrink) {
+    const int n = reduce_points(shrink);
+    if (n > 16) return {};  // k_hmfma: a 16-byte fragment window holds every tap
+    const size_t rows_bytes = static_cast<size_t>(kTransformScale + 1) * 2 * kHmTabW;
+    std::vector<int> t;
+    reduce_table(shrink, t);
+    HostTable r;
+    r.bytes.assign(rows_bytes + (kTransformScale + 1) * sizeof(int), 0);
+    for (int ph = 0; ph <= kTransformScale; ++ph) {
+        uint8_t *row = r.bytes.data() + static_cast<size_t>(ph) * 2 * kHmTabW + kHmTabPad;
+        int sum = 0;
+        for (int i = 0; i < n; ++i) {
+            const int c = t[static_cast<size_t>(ph) * n + i];
+            sum += c;
+            split_tap(c, row + i, row + kHmTabW + i);
+        }
+        std::memcpy(r.bytes.data() + rows_bytes + ph * sizeof(int), &sum, sizeof(int));
+    }
+    r.meta[0] = n;
+    r.meta[1] = static_cast<int>(rows_bytes);
+    return r;
+}
+
+// The same split taps at a byte stride of `bands` (k_rmf4's horizontal products on
+// interleaved pixel bytes): row (phase, hi / lo) holds tap i at byte kRsTabPad + bands * i,
+// zeros elsewhere, so a 16-byte window at any offset in [-kRsTabPad, 64) is an MFMA
+// fragment of one output byte's taps.
+HostTable build_reduce_i8s(double shrink, int bands) {
+    const int n = reduce_points(shrink);
+    if (n > 16 || bands < 1 || bands > 4) return {};
+    std::vector<int> t;
+    reduce_table(shrink, t);
+    HostTable r;
+    r.bytes.assign(static_cast<size_t>(kTransformScale + 1) * 2 * kRsTabW, 0);
+    for (int ph = 0; ph <= kTransformScale; ++ph) {
+        uint8_t *row = r.bytes.data() + static_cast<size_t>(ph) * 2 * kRsTabW + kRsTabPad;
+        for (int i = 0; i < n; ++i) split_tap(t[static_cast<size_t>(ph) * n + i], row + bands * i, row + kRsTabW + bands * i);
+    }
+    r.meta[0] = n;
+    return r;
+}
+
+// The stride-B split taps with libvips' COPY edge folded in (k_rcol's edge operands):
+// rows [2 sides][taps - 1 amounts][129 phases][hi, lo][kRsTabW]; side 0 is fold_left by the
+// amount, side 1 fold_right.
+HostTable build_reduce_i8s_fold(double shrink, int bands) {
+    const int n = reduce_points(shrink);
+    if (n > 16 || n < 2 || bands < 1 || bands > 4) return {};
+    std::vector<int> t;
+    reduce_table(shrink, t);
+    const size_t per_side = static_cast<size_t>(n - 1) * (kTransformScale + 1) * 2 * kRsTabW;
+    HostTable r;
+    r.bytes.assign(2 * per_side, 0);
+    std::vector<int> f(n);
+    for (int side = 0; side < 2; ++side)
+        for (int a = 1; a < n; ++a)
+            for (int ph = 0; ph <= kTransformScale; ++ph) {
+                const int *c = t.data() + static_cast<size_t>(ph) * n;
+                if (side == 0) fold_left(c, n, a, f.data());
+                else fold_right(c, n, a, f.data());
+                uint8_t *row = r.bytes.data() + side * per_side +
+                               ((static_cast<size_t>(a - 1) * (kTransformScale + 1) + ph) * 2) * kRsTabW + kRsTabPad;
+                for (int k = 0; k < n; ++k) split_tap(f[k], row + bands * k, row + kRsTabW + bands * k);
+            }
+    r.meta[0] = n;
+    return r;
+}
+
+// k_rcol's vertical plan for one shrink and sampling convention over output rows
+// 0 .. cap - 1: per output row o, kRcolPlanRow bytes = [64 hi][64 lo] i8 taps placed
+// at the K index of their input row relative to the first input row of o's 16-row
+// group (K index 16 g + e holds relative row 8 g + e for e < 8, 32 + 8 g + e - 8
+// otherwise: the transposed LDS reads' row order), the accumulator seed
+// 128 * sum + 2048 - (128 << 12) (pixels enter as p - 128, the result leaves as u8 - 128),
+// 12 pad bytes; then per 16-row group k two ints: its first input row start(16 k) and
+// its end start(16 k + 15) + taps.  cap = 1024 << k, the first that holds the rows asked for.
+HostTable build_rcol_vplan(double shrink, bool centre, int rows) {
+    const int n = reduce_points(shrink);
+    if (rows <= 0 || n > 16) return {};
+    int cap = 1024;
+    while (cap < rows) cap *= 2;
+    std::vector<int> t;
+    reduce_table(shrink, t);
+    const int pad = n / 2 - 1;
+    auto start = [&](int o, int *phase) { return reduce_pos(o, shrink, centre, pad, phase); };
+    const size_t rows_bytes = static_cast<size_t>(cap) * kRcolPlanRow;
+    HostTable r;
+    std::vector<uint8_t> &h = r.bytes;
+    h.assign(rows_bytes + static_cast<size_t>(cap / 16) * 2 * sizeof(int), 0);
+    for (int o = 0; o < cap; ++o) {
+        int ph = 0;
+        const int d = start(o, &ph) - start(o & ~15, nullptr);
+        const int *c = t.data() + static_cast<size_t>(ph) * n;
+        uint8_t *row = h.data() + static_cast<size_t>(o) * kRcolPlanRow;
+        int sum = 0;
+        for (int i = 0; i < n; ++i) sum += c[i];
+        for (int k = 0; k < 64; ++k) {
+            const int e = k & 15, g = k >> 4;
+            const int rel = e < 8 ? 8 * g + e : 32 + 8 * g + e - 8;
+            const int ti = rel - d;
+            split_tap(ti >= 0 && ti < n ? c[ti] : 0, row + k, row + 64 + k);
+        }
+        const int seed = 128 * sum + 2048 - (128 << 12);
+        std::memcpy(row + 128, &seed, sizeof(int));
+    }
+    for (int k = 0; k < cap / 16; ++k) {
+        const int se[2] = {start(16 * k, nullptr), start(16 * k + 15, nullptr) + n};
+        std::memcpy(h.data() + rows_bytes + static_cast<size_t>(k) * 2 * sizeof(int), se, sizeof(se));
+    }
+    r.rows = cap;
+    return r;
+}
+
+// k_rcol's host-built horizontal operands of one window geometry (r06).  The same
+// arithmetic as k_rcol's set-up (positions as separately rounded doubles: this file is
+// built without FP contraction, as the oracle).  Per 64-pixel strip, per 16-byte output unit
+// u < 4 bands, per lane: per K step the hi / lo tap fragments (COPY edge folded, odd K
+// blocks' halves swapped), then the four per-byte seeds, kRcolHopRec(nks) bytes; then per
+// (strip, unit) the K origin (int).
+size_t rcol_hops_bytes(int bands, int ow, int nks) {
+    const size_t units = static_cast<size_t>((ow + 63) / 64) * 4 * bands;
+    return units * 64 * kRcolHopRec(nks) + units * sizeof(int);
+}
+
+HostTable build_rcol_hops(double hs, int bands, bool centre, int ox0, int ow, int w, int k4, int nks) {
+    if (ow <= 0 || w <= 0 || bands < 3 || bands > 4 || nks < 1 || nks > 2) return {};
+    const size_t rsz = kRcolHopRec(nks);
+    const int n = reduce_points(hs), B = bands, pad = n / 2 - 1;
+    if (n > 16 || n < 2) return {};
+    const int ns = (ow + 63) / 64, units = 4 * B;
+    const size_t recs = static_cast<size_t>(ns) * units * 64;
+    std::vector<int> t;
+    reduce_table(hs, t);
+    std::vector<int> sums(kTransformScale + 1, 0);
+    for (int ph = 0; ph <= kTransformScale; ++ph)
+        for (int i = 0; i < n; ++i) sums[ph] += t[static_cast<size_t>(ph) * n + i];
+    auto pos = [&](int o, int *ph) { return reduce_pos(o, hs, centre, pad, ph); };
+    HostTable r;
+    std::vector<uint8_t> &h = r.bytes;
+    h.assign(rcol_hops_bytes(B, ow, nks), 0);
+    int *kbs = reinterpret_cast<int *>(h.data() + recs * rsz);
+    std::vector<int> f(n);
+    for (int s = 0; s < ns; ++s) {
+        const int x0 = 64 * s, x_last = std::min(x0 + 63, ow - 1);
+        int ph = 0;
+        const int lo = pos(ox0 + x0, &ph);
+        const int org = lo & (lo < 0 && B == 3 ? ~15 : ~3);
+        for (int u = 0; u < units; ++u) {
+            const int sf = pos(ox0 + std::min(x0 + (16 * u) / B, x_last), &ph);
+            const int kb = (B * (sf - org) + (16 * u) % B) & (k4 ? ~3 : ~7);
+            kbs[s * units + u] = kb;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int nn = lane & 15, kg = lane >> 4;
+                uint8_t *rec = h.data() + ((static_cast<size_t>(s) * units + u) * 64 + lane) * rsz;
+                const int o = 16 * u + nn, xl = o / B, c = o - B * xl;
+                int pp = 0;
+                const int sp = pos(ox0 + std::min(x0 + xl, x_last), &pp);
+                const int *cr = t.data() + static_cast<size_t>(pp) * n;
+                const int lfold = -sp, rfold = sp + n - 1 - (w - 1);
+                const bool both = lfold > 0 && rfold > 0;
+                // the tap row k_rcol reads: plain, or the COPY edge folded onto pixel 0 / w - 1
+                if (!both && lfold > 0) fold_left(cr, n, lfold, f.data());
+                else if (!both && rfold > 0) fold_right(cr, n, rfold, f.data());
+                else std::copy(cr, cr + n, f.begin());
+                for (int ks = 0; ks < nks; ++ks) {
+                    const int j0 = kb + 64 * ks + 16 * kg;
+                    uint8_t fh[16], fl[16];
+                    for (int e = 0; e < 16; ++e) {
+                        int v = 0;
+                        const int d = j0 + e - c;
+                        if (both) {  // images narrower than the mask (rc_edge_frag)
+                            if (d >= 0 && d % B == 0) {
+                                const int p = org + d / B;
+                                if (p >= 0 && p <= w - 1)
+                                    for (int k = 0; k < n; ++k)
+                                        if (std::min(std::max(sp + k, 0), w - 1) == p) v += cr[k];
+                            }
+                        } else {
+                            const int rr = d - B * (sp - org);  // tap k sits at rr = B k
+                            if (rr >= 0 && rr % B == 0 && rr / B < n) v = f[rr / B];
+                        }
+                        split_tap(v, fh + e, fl + e);
+                    }
+                    // odd K blocks read their second 8 bytes first (k_rcol's swz)
+                    const int sw = (kg & 1) ? 8 : 0;
+                    for (int e = 0; e < 16; ++e) {
+                        rec[32 * ks + e] = fh[(e + sw) & 15];
+                        rec[32 * ks + 16 + e] = fl[(e + sw) & 15];
+                    }
+                }
+                const int eb = 16 * u + 4 * kg;
+                for (int j = 0; j < 4; ++j) {
+                    int p2 = 0;
+                    pos(ox0 + std::min(x0 + (eb + j) / B, x_last), &p2);
+                    const int seed = 128 * sums[p2] + 2048;
+                    std::memcpy(rec + 32 * nks + 4 * j, &seed, sizeof(int));
+                }
+            }
+        }
+    }
+    r.meta[0] = ns;
+    return r;
+}
+
+// k_bmf operands (i8, 16 bytes per lane in the v_mfma_i32_16x16x64_i8 layouts):
+// [nks][64 lanes] horizontal A: lane l row m = l & 15 (output byte), K bytes
+// 64 ks + 16 (l >> 4) + j hold tap k where K = m + delta + bands * k; then
+// [64 lanes] vertical B: K index 16 (l >> 4) + j holds relative row R = K (vperm 0) or
+// R = 8 (l >> 4) + j (j < 8) / 32 + 8 (l >> 4) + j - 8 (vperm 1, k_bcol's transposed reads
+// of consecutive rows); output row l & 15 holds tap R - row.
+HostTable build_blur_ops(const std::vector<int> &mask, int bands, int delta, int nks, int vperm) {
+    const int n = static_cast<int>(mask.size());
+    HostTable r;
+    std::vector<uint8_t> &h = r.bytes;
+    h.assign(static_cast<size_t>(nks + 1) * 64 * 16, 0);
+    const auto i8 = [](int v) { return static_cast<uint8_t>(static_cast<signed char>(v)); };
+    for (int ks = 0; ks < nks; ++ks)
+        for (int l = 0; l < 64; ++l)
+            for (int j = 0; j < 16; ++j) {
+                const int m = l & 15, kk = 64 * ks + 16 * (l >> 4) + j - m - delta;
+                if (kk >= 0 && kk % bands == 0 && kk / bands < n) h[(static_cast<size_t>(ks) * 64 + l) * 16 + j] = i8(mask[kk / bands]);
+            }
+    for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 16; ++j) {
+            const int rel = vperm ? (j < 8 ? 8 * (l >> 4) + j : 32 + 8 * (l >> 4) + j - 8) : 16 * (l >> 4) + j;
+            const int k = rel - (l & 15);
+            if (k >= 0 && k < n) h[(static_cast<size_t>(nks) * 64 + l) * 16 + j] = i8(mask[k]);
+        }
+    return r;
+}
+
+// float copy of the integer gaussmat mask; scale = mask sum
+HostTable build_gauss_table(double sigma, double min_ampl) {
+    std::vector<int> mask;
+    int sc = 0;
+    const int n = gaussmat(sigma, min_ampl, mask, sc);
+    if (n <= 0) return {};
+    HostTable r;
+    r.bytes = as_bytes(std::vector<float>(mask.begin(), mask.end()));
+    r.meta[0] = n;
+    r.meta[1] = sc;
+    return r;
+}
+
+// [256 v2y | kQuantElements cbrt | 257 y2v] floats
+HostTable build_colour_tables() {
+    std::vector<float> h(256 + kQuantElements + 257);
+    std::memcpy(h.data(), v2y8_table(), 256 * sizeof(float));
+    std::memcpy(h.data() + 256, cbrt_table(), kQuantElements * sizeof(float));
+    std::memcpy(h.data() + 256 + kQuantElements, y2v8_table(), 257 * sizeof(float));
+    HostTable r;
+    r.bytes = as_bytes(h);
+    return r;
+}
+
+HostTable build_bicubic_table() {
+    std::vector<int> t((kTransformScale + 1) * 4);
+    bicubic_table(t.data());
+    HostTable r;
+    r.bytes = as_bytes(t);
+    return r;
+}
+
+}  // namespace mipx

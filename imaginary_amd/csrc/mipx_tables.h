@@ -1,0 +1,65 @@
+// mipx_tables.h — the libvips table maths and the host builders of every device-resident
+// table (mipx_tables.cpp, mipx_planner.cpp).  No HIP here: a plain host program can build and
+// check every table (tests/c/tables_host.cpp).  mipx_device_tables.cpp uploads and caches what
+// the builders return.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace mipx {
+
+// ---- libvips resample constants (resample/templates.h, [U]) ----------------
+constexpr int kTransformScale = 128;  // VIPS_TRANSFORM_SCALE: 129 sub-pixel phases
+constexpr int kInterpShift = 12;      // VIPS_INTERPOLATE_SHIFT
+constexpr int kInterpScale = 1 << kInterpShift;
+
+// Lanczos3 reduce geometry (libvips reduceh.cpp / reducev.cpp).
+int reduce_points(double shrink);                      // 2 * rint(3 * shrink) + 1
+void reduce_table(double shrink, std::vector<int> &t); // 129 x n truncated 12-bit taps
+int out_size_reduce(int in, double shrink);            // VIPS_ROUND(in / shrink)
+int out_size_shrink(int in, int shrink);               // VIPS_ROUND(in / shrink)
+// where output o of a reduce samples its input, under the corner or the centre convention
+inline double reduce_x_host(int o, double s, bool centre) { return centre ? (o + 0.5) * s - 0.5 : o * s; }
+
+// Integer gaussmat (libvips create/gaussmat.c): returns width, fills mask/scale.
+int gaussmat(double sigma, double min_ampl, std::vector<int> &mask, int &scale);
+
+// Colour LUTs for the smartcrop scorer (libvips colour/*.c, [U]).
+constexpr int kQuantElements = 100000;
+const float *v2y8_table();    // 256 entries: sRGB 8-bit -> linear
+const float *cbrt_table();    // kQuantElements entries: Lab f(t)
+const float *y2v8_table();    // 257 entries: linear Y x 255 -> sRGB 8-bit (B_W)
+void bicubic_table(int *t);   // 129 x 4 bicubic taps (vips_affine)
+
+// ---- table layouts the kernels share with the builders -----------------------
+constexpr int kHmTabW = 64;     // k_hmfma i8 tap rows: bytes per (phase, hi / lo) row (16.5 KB: L1-resident)
+constexpr int kHmTabPad = 16;   // zero bytes in front of tap 0 (taps <= 16; windows clamped to [-16, 16])
+constexpr int kRsTabPad = 128;  // k_rmf4 stride-B tap rows: zero bytes in front of tap 0
+constexpr int kRsTabW = 272;    // bytes per (phase, hi / lo) row: pad + 2 K steps + a fragment (70 KB per table)
+constexpr int kRcolPlanRow = 144;                              // k_rcol's vertical plan: bytes per output row
+constexpr int kRcolHopRec(int nks) { return 32 * nks + 16; }   // k_rcol's horizontal operands: bytes per lane record
+
+// ---- host builders (mipx_tables.cpp) --------------------------------------------
+// What a builder returns: the table as it goes to the device, and what its fetcher reports
+// besides the pointer.  No bytes = no such table (parameters outside what the kernel takes).
+struct HostTable {
+    std::vector<uint8_t> bytes;
+    int meta[2] = {0, 0};
+    int rows = 0;  // growable tables: the rows this build holds
+};
+HostTable build_reduce_table(double shrink);                       // meta: taps
+HostTable build_reduce_pairs(double shrink);                       // meta: taps, tpa
+HostTable build_reduce_i8(double shrink);                          // meta: taps, byte offset of the sums
+HostTable build_reduce_i8s(double shrink, int bands);              // meta: taps
+HostTable build_reduce_i8s_fold(double shrink, int bands);         // meta: taps
+HostTable build_rcol_vplan(double shrink, bool centre, int rows);  // rows: 1024 << k >= rows asked for
+size_t rcol_hops_bytes(int bands, int ow, int nks);                // size of the next one's table
+HostTable build_rcol_hops(double hs, int bands, bool centre, int ox0, int ow, int w, int k4, int nks);  // meta: strips
+HostTable build_blur_ops(const std::vector<int> &mask, int bands, int delta, int nks, int vperm);
+HostTable build_gauss_table(double sigma, double min_ampl);        // meta: taps, scale
+HostTable build_colour_tables();
+HostTable build_bicubic_table();
+
+}  // namespace mipx
