@@ -118,6 +118,64 @@ def decode(buf: bytes, shrink: int = 1) -> np.ndarray:
     return a[:, :, None] if a.ndim == 2 else np.ascontiguousarray(a)
 
 
+YCC_444 = 0   # MIPX_YCC_444: Cb and Cr at full size
+YCC_420 = 1   # MIPX_YCC_420: Cb and Cr at ceil(w / 2) x ceil(h / 2)
+
+
+def decode_ycc(buf: bytes):
+    """A JPEG's planes as the decoder has them before its upsample and colour conversion,
+    packed for the engine's MIPX_OP_YCC step: (planes, layout) with planes a 1-D uint8 array
+    of Y (h x w), then Cb, then Cr (ch x cw each), or None when the file is anything but a
+    3-component YCbCr JPEG sampled 4:4:4 or 4:2:0 (the caller then takes decode()).
+
+    Stand-in recipe: Pillow's libjpeg hands out YCbCr unconverted (draft "YCbCr"); for 4:2:0
+    a second decode at scale 1/2 runs chroma through its full 8 x 8 IDCT with no upsampling,
+    so its channels 1 and 2 are the raw chroma planes.  A real shim reads them in one decode
+    (TurboJPEG tjDecompressToYUVPlanes, or libjpeg jpeg_read_raw_data)."""
+    if _PIL is None or sniff_type(buf) != "jpeg":
+        return None
+    try:
+        from PIL import JpegImagePlugin
+        im = _open(buf)
+        if im.format != "JPEG" or im.mode != "RGB" or getattr(im, "layers", 0) != 3:
+            return None
+        if im.info.get("adobe_transform") == 0:   # Adobe marker, transform 0: the components are RGB
+            return None
+        if ("jfif" not in im.info and "adobe" not in im.info
+                and [c[0] for c in getattr(im, "layer", [])] == [82, 71, 66]):
+            return None   # no JFIF / Adobe marker and component ids 'R' 'G' 'B': libjpeg takes it as RGB
+        layout = {0: YCC_444, 2: YCC_420}.get(JpegImagePlugin.get_sampling(im))
+        if layout is None:
+            return None
+        w, h = im.size
+        im.draft("YCbCr", (w, h))
+        full = np.asarray(im, dtype=np.uint8)
+        if im.mode != "YCbCr" or full.shape != (h, w, 3):
+            return None
+        if layout == YCC_444:
+            cb, cr = full[:, :, 1], full[:, :, 2]
+        else:
+            cw, ch = (w + 1) // 2, (h + 1) // 2
+            half = _open(buf)
+            half.draft("YCbCr", (max(w // 2, 1), max(h // 2, 1)))
+            c = np.asarray(half, dtype=np.uint8)
+            if half.decoderconfig[0] == 1:
+                # a 1-pixel-wide or -high image cannot be drafted to 1/2.  With cw <= 2 libjpeg
+                # replicates chroma, so every second sample of the full decode is the raw plane;
+                # wider ones are interpolated and this stand-in cannot get at their planes.
+                if min(w, h) > 1 or cw > 2:
+                    return None
+                c = c[::2, ::2]
+            elif half.decoderconfig[0] != 2:
+                return None
+            if half.mode != "YCbCr" or c.shape != (ch, cw, 3):
+                return None
+            cb, cr = c[:, :, 1], c[:, :, 2]
+    except Exception:  # noqa: BLE001 - whatever the planar decode cannot do, the RGB decode reports
+        return None
+    return np.concatenate([full[:, :, 0].ravel(), cb.ravel(), cr.ravel()]), layout
+
+
 _SANS_FACES = ("DejaVuSans.ttf", "LiberationSans-Regular.ttf", "NotoSans-Regular.ttf", "FreeSans.ttf", "Arial.ttf")
 DEFAULT_FONT_POINTS = 10.0
 

@@ -197,6 +197,8 @@ int watermark_launch(const uint8_t *base, const uint8_t *wm, uint8_t *out, int n
 // k_textmark.hip: the rendered text mask (tw x th x 1) tiled and blended in; 1 or 3 bands -> 3
 int textmark_launch(const uint8_t *in, const uint8_t *mask, uint8_t *out, int n, int w, int h, int bands, int tw,
                     int th, int margin, float opacity, const int *colour, hipStream_t st);
+// k_ycc.hip: packed JPEG planes (MIPX_YCC_*) -> RGB
+int ycc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, hipStream_t st);
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,
@@ -205,6 +207,10 @@ int smartcrop_extract(const uint8_t *in, uint8_t *out, int n, int w, int h, int 
                       size_t ws_bytes, hipStream_t st);
 // mipx_ops.cpp
 size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, double p1);
+
+// mipx_planner.cpp: bytes per image of the plan's input buffer: w * h * bands, or the packed
+// planes when step 0 is MIPX_OP_YCC (header fields already validated)
+size_t plan_input_bytes(const mipx_plan *p);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -608,6 +608,43 @@ extern "C" int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t m
     return MIPX_OK;
 }
 
+// ---- planar JPEG input (MIPX_OP_YCC) ---------------------------------------------
+extern "C" size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout) {
+    if (w <= 0 || h <= 0 || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return 0;
+    const size_t cw = layout == MIPX_YCC_420 ? (static_cast<size_t>(w) + 1) / 2 : w;
+    const size_t ch = layout == MIPX_YCC_420 ? (static_cast<size_t>(h) + 1) / 2 : h;
+    return static_cast<size_t>(w) * h + 2 * cw * ch;
+}
+
+size_t mipx::plan_input_bytes(const mipx_plan *p) {
+    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_YCC) return mipx_ycc_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
+    return static_cast<size_t>(p->in_w) * p->in_h * p->in_bands;
+}
+
+extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
+    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (plan->in_bands != 3) {
+        mipx::set_error("mipx_plan_set_ycc_input: the plan takes %d bands, planar YCbCr makes 3", plan->in_bands);
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps > 0 && plan->steps[0].op == MIPX_OP_YCC) {
+        mipx::set_error("mipx_plan_set_ycc_input: the plan already takes planar input");
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps >= MIPX_MAX_STEPS) {
+        mipx::set_error("mipx_plan_set_ycc_input: the plan is full (MIPX_MAX_STEPS)");
+        return MIPX_EINVAL;
+    }
+    for (int i = plan->n_steps; i > 0; --i) plan->steps[i] = plan->steps[i - 1];
+    ++plan->n_steps;
+    mipx_step &s = plan->steps[0];
+    std::memset(&s, 0, sizeof(s));
+    s.op = MIPX_OP_YCC;
+    s.a[0] = layout;
+    s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = 3;
+    return MIPX_OK;
+}
+
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {
     if (!stages || !out || n_stages <= 0) return MIPX_EINVAL;
     mipx_plan m{};
@@ -627,8 +664,13 @@ extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_p
             return MIPX_EINVAL;
         }
         bool wm = false;
-        for (int i = 0; i < s.n_steps; ++i)
+        for (int i = 0; i < s.n_steps; ++i) {
             wm |= s.steps[i].op == MIPX_OP_WATERMARK || s.steps[i].op == MIPX_OP_TEXTMARK;
+            if (k > 0 && s.steps[i].op == MIPX_OP_YCC) {  // only the request's input can be planes
+                mipx::set_error("mipx_plan_chain: stage %d takes planar input; only stage 0 may", k);
+                return MIPX_EINVAL;
+            }
+        }
         wm_stages += wm;
         if (wm_stages > 1) {
             mipx::set_error("mipx_plan_chain: more than one watermark stage");

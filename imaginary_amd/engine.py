@@ -11,10 +11,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, sync_tuning)
+                   EXTEND, GRAVITY, TYPES, OP_YCC, YCC_444, YCC_420, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
+           "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -265,6 +266,34 @@ def plan_add_textmark(plan: MipxPlan, mask_w: int, mask_h: int, margin: int, opa
     return plan
 
 
+def ycc_bytes(w: int, h: int, layout: int) -> int:
+    """mipx_ycc_bytes: bytes of one image's packed planes (0 for bad arguments)."""
+    return int(lib.mipx_ycc_bytes(w, h, layout))
+
+
+def plan_set_ycc_input(plan: MipxPlan, layout: int) -> MipxPlan:
+    """mipx_plan_set_ycc_input on `plan` (in place; returned for convenience): the plan then
+    takes packed JPEG planes (Y, Cb, Cr; YCC_444 or YCC_420) instead of RGB pixels."""
+    check(lib.mipx_plan_set_ycc_input(C.byref(plan), layout), "mipx_plan_set_ycc_input")
+    return plan
+
+
+def _ycc_layout(plan: MipxPlan):
+    """The plane layout a plan's input has, or None for interleaved pixels."""
+    return plan.steps[0].a[0] if plan.n_steps > 0 and plan.steps[0].op == OP_YCC else None
+
+
+def _planes(plan: MipxPlan, planes) -> np.ndarray:
+    """A YCC plan's input as (n, bytes) uint8, from (bytes,) or (n, bytes)."""
+    x = np.ascontiguousarray(planes, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x[None]
+    need = ycc_bytes(plan.in_w, plan.in_h, _ycc_layout(plan))
+    if x.ndim != 2 or x.shape[1] != need:
+        raise ValueError(f"planar input of shape {np.shape(planes)}: the plan takes ({need},) or (n, {need}) uint8")
+    return x
+
+
 def fit_dimension(iw, ih, fw, fh):
     a, b = C.c_int32(), C.c_int32()
     check(lib.mipx_fit_dimension(iw, ih, fw, fh, C.byref(a), C.byref(b)), "mipx_fit_dimension")
@@ -309,8 +338,13 @@ class Engine:
         result: contiguous uint8 of the plan's output shape.  The MIPX_* kernel knobs are
         re-read in Engine(), run_op and execute, not per request: a reload
         must not race the queue workers' launches."""
-        if not (img.dtype == np.uint8 and img.ndim == 3 and img.strides[2] == 1
-                and img.strides[1] == img.shape[2]):
+        planar = _ycc_layout(plan) is not None
+        if planar:  # the packed planes of one image, described as the plan's w x h x 3
+            img = _planes(plan, img)
+            if img.shape[0] != 1:
+                raise ValueError("submit takes one image's planes")
+        elif not (img.dtype == np.uint8 and img.ndim == 3 and img.strides[2] == 1
+                  and img.strides[1] == img.shape[2]):
             img = np.ascontiguousarray(img, dtype=np.uint8)  # rows may keep a wider stride
         shape = (plan.out_h, plan.out_w, plan.out_bands)
         if out is None:
@@ -319,7 +353,8 @@ class Engine:
             raise ValueError(f"out must be contiguous uint8 {shape}")
         ti = C.c_uint64()
         wmi = C.byref(_img(np.ascontiguousarray(wm, dtype=np.uint8))) if wm is not None else None
-        check(lib.mipx_submit(device, C.byref(plan), C.byref(_img(img)), wmi, C.byref(_img(out)),
+        src = MipxImg(img.ctypes.data, plan.in_w, plan.in_h, 3, 0) if planar else _img(img)
+        check(lib.mipx_submit(device, C.byref(plan), C.byref(src), wmi, C.byref(_img(out)),
                               C.byref(ti)), "mipx_submit")
         return ti.value, out
 
@@ -460,6 +495,25 @@ def run_op(name: str, imgs: np.ndarray, **p) -> np.ndarray:
     return dout.download((n, oh, ow, ob))
 
 
+def ycc_to_rgb(planes: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
+    """mipx_op_ycc_to_rgb on packed planes, (bytes,) or (n, bytes) uint8; returns (n, h, w, 3)."""
+    sync_tuning()
+    x = np.ascontiguousarray(planes, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x[None]
+    need = ycc_bytes(w, h, layout)
+    if x.ndim != 2 or need == 0 or x.shape[1] != need:
+        raise ValueError(f"planes of shape {np.shape(planes)} for {w}x{h} layout {layout}: {need} bytes per image")
+    n = x.shape[0]
+    what = "mipx_op_ycc_to_rgb"
+    din = _dev("in", what, x.nbytes, w, x)
+    dout = _dev("out", what, n * h * w * 3, w * 3)
+    check(lib.mipx_op_ycc_to_rgb(din.ptr, dout.ptr, n, w, h, layout, None), what)
+    synchronize()
+    _check_guards(what, din, dout)
+    return dout.download((n, h, w, 3))
+
+
 def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
     sync_tuning()
     x = _batch(imgs)
@@ -477,14 +531,16 @@ def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
 
 def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
             junk: Optional[int] = None) -> np.ndarray:
-    """mipx_execute_dev on a batch of host images (uploads, runs the plan, downloads).
+    """mipx_execute_dev on a batch of host images (uploads, runs the plan, downloads); for a
+    plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes).
     junk: fill the workspace (the ping-pong intermediates) and the output with this byte
     first, so a step that reads outside what the steps before it wrote shows up."""
     sync_tuning()
-    x = _batch(imgs)
+    planar = _ycc_layout(plan) is not None
+    x = _planes(plan, imgs) if planar else _batch(imgs)
     n = x.shape[0]
     what = "mipx_execute_dev"
-    din = _dev("in", what, x.nbytes, x.shape[2] * x.shape[3], x)
+    din = _dev("in", what, x.nbytes, plan.in_w if planar else x.shape[2] * x.shape[3], x)
     dout = _dev("out", what, n * plan.out_w * plan.out_h * plan.out_bands, plan.out_w * plan.out_bands)
     wsb = lib.mipx_workspace_bytes(C.byref(plan), n)
     ws = _dev("ws", what, wsb) if wsb else None

@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _abi, codec
 from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_textmark, plan_chain, plan_make,
-                     plan_textmark_geometry)
+                     plan_set_ycc_input, plan_textmark_geometry)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -480,7 +480,7 @@ def _add_textmark(plan, t: TextMark) -> np.ndarray:
 
 
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
-            text: Optional[TextMark] = None):
+            text: Optional[TextMark] = None, ycc: Optional[tuple] = None):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -491,7 +491,9 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     watermark) is appended and placeholder pixels of the output shape returned
     (Pipeline fuses the stages into one device-resident plan).
     With `text`, the plan gets a text watermark step and the rendered mask takes the
-    watermark slot."""
+    watermark slot.
+    With `ycc` = (planes, layout) (codec.decode_ycc), a Decoded input's pixels are only a
+    shape: the plan takes the JPEG's packed planes and the engine upsamples and converts."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         return process_bytes(bytes(img), opts, wm, text)
     opts = {k: v for k, v in opts.items() if k not in _ENCODE_ONLY}
@@ -513,6 +515,11 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
             raise ImaginaryError("decoded size does not match the header", 500)
         if text is not None:
             wm = _add_textmark(plan, text)
+        if ycc is not None:
+            if plan.load_shrink > 1 or chain is not None:
+                raise ImaginaryError("planar input needs the full-size decode of a single request", 500)
+            plan_set_ycc_input(plan, ycc[1])
+            px = ycc[0]
         if chain is not None:
             chain.append((plan, px, wm))
             return _placeholder(plan.out_h, plan.out_w, plan.out_bands)
@@ -523,10 +530,14 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
         raise ImaginaryError(f"image processing error: {e}", 500) from e
 
 
-def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None) -> Image:
+def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
+                  ycc: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
-    retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112)."""
+    retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
+    ycc: hand a 4:4:4 or 4:2:0 YCbCr JPEG to the engine as its planes (codec.decode_ycc), half
+    the upload of RGB for 4:2:0, when the request decodes at full size; the bytes are the
+    same either way.  Shrink-on-load requests and every other file keep the RGB decode."""
     opts = dict(opts)
     out_type = str(opts.pop("type", "") or "")
     quality = int(opts.pop("quality", 0) or 0)
@@ -560,7 +571,12 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
         px = process(src, opts, wm=wm_px, redecode=redecode, text=text)
     else:
-        px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text)
+        planes = codec.decode_ycc(buf) if ycc and hdr.bands == 3 else None
+        if planes is not None:
+            px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
+                         ycc=planes)
+        else:
+            px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text)
     t = out_type or (hdr.type if hdr.type in ("jpeg", "png", "webp", "gif", "tiff") else "png")
     try:
         body = codec.encode(px, t, quality or None, compression)

@@ -36,6 +36,8 @@
  *    on 4-band images mipx_op_rot and mipx_op_embed (and mipx_op_flip on images of
  *    2 GiB or more, or more than 65535 rows), per op or as a plan step, take 4-byte
  *    aligned input and output pointers only and return MIPX_EINVAL for others.
+ *    A plan that starts with MIPX_OP_YCC, and mipx_op_ycc_to_rgb, read n * mipx_ycc_bytes()
+ *    input bytes instead (packed JPEG planes, see MIPX_YCC_*), at any alignment.
  *  - Thread-safe: mipx_submit / mipx_wait / mipx_process may be called from
  *    many threads (one goroutine per HTTP request).
  */
@@ -124,10 +126,22 @@ enum {
     MIPX_OP_ZOOM,        /* a[0] = xfac, a[1] = yfac                         (vips_zoom) */
     MIPX_OP_FLATTEN,     /* a[0..2] = background rgb                         (vips_flatten) */
     MIPX_OP_BW,          /* sRGB -> B_W                                      (vips_colourspace) */
-    MIPX_OP_TEXTMARK     /* a[0..1] = mask w, h; a[2] = margin; a[3..5] = colour; d[0] = opacity after
+    MIPX_OP_TEXTMARK,    /* a[0..1] = mask w, h; a[2] = margin; a[3..5] = colour; d[0] = opacity after
                             defaulting; out_bands = 3; the rendered text mask travels as the request's
                             watermark image (a[0] x a[1] x 1)              (bimg vips_watermark) */
+    MIPX_OP_YCC          /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, whose input
+                            buffer is then the packed planes (mipx_plan_set_ycc_input)
+                                                     (libjpeg upsample + colour conversion) */
 };
+
+/* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
+ * (libjpeg jpeg_read_raw_data, TurboJPEG tjDecompressToYUVPlanes).  One image is Y, h rows
+ * of w bytes, then Cb, then Cr, ch rows of cw bytes each: no row, plane or image padding, so
+ * planes and images start on any byte.  MIPX_YCC_444: cw = w, ch = h.  MIPX_YCC_420:
+ * cw = ceil(w / 2), ch = ceil(h / 2).  The engine upsamples 4:2:0 chroma as libjpeg's
+ * default "fancy" h2v2 upsampler does (plain replication when cw <= 2) and converts with
+ * libjpeg's integer YCbCr -> RGB, bit for bit (PARITY_ASSUMPTIONS.md row 16). */
+enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
 
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
 typedef struct mipx_step {
@@ -200,6 +214,19 @@ int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out);
 int mipx_plan_textmark_geometry(const mipx_plan *plan, int32_t *w, int32_t *h, int32_t *bands);
 int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t mask_h, int32_t margin, float opacity,
                            const int32_t *colour3, int32_t no_replicate);
+/* Planar JPEG input (MIPX_YCC_*).  Both calls work without a GPU.
+ * mipx_ycc_bytes: bytes of one w x h image's packed planes, w * h + 2 * cw * ch; 0 for a
+ * non-positive size or an unknown layout.
+ * mipx_plan_set_ycc_input: inserts the MIPX_OP_YCC step at index 0 of a 3-band plan (the other
+ * steps move up).  The plan's geometry (in_w, in_h, in_bands, out_*) is unchanged; what
+ * changes is the input buffer, which is then mipx_ycc_bytes(in_w, in_h, layout) bytes per
+ * image for mipx_execute_dev, and for mipx_submit a mipx_img of w = in_w, h = in_h, bands = 3,
+ * stride = 0 whose data is the packed planes (anything else is MIPX_EINVAL).  Use it on plans
+ * with load_shrink 1 (the planes are the full-size decode).  In a mipx_plan_chain the step may
+ * appear in stage 0 only.  MIPX_EINVAL for an unknown layout, in_bands != 3, a plan that
+ * already starts with the step, or a full plan. */
+size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout);
+int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout);
 /* imaginary image.go:190 calculateDestinationFitDimension */
 int mipx_fit_dimension(int32_t image_w, int32_t image_h, int32_t fit_w, int32_t fit_h,
                        int32_t *out_w, int32_t *out_h);
@@ -267,6 +294,12 @@ int mipx_op_watermark(const uint8_t *d_base, const uint8_t *d_wm, uint8_t *d_out
 int mipx_op_text_watermark(const uint8_t *d_in, const uint8_t *d_mask, uint8_t *d_out, int32_t n,
                            int32_t w, int32_t h, int32_t bands, int32_t mask_w, int32_t mask_h,
                            int32_t margin, float opacity, const int32_t *colour3, void *stream);
+/* n images of packed planes (n * mipx_ycc_bytes(w, h, layout) bytes) -> n x h x w x 3 RGB; both
+ * pointers at any alignment.  MIPX_EINVAL, before any HIP call, for NULL pointers, n <= 0, a
+ * non-positive size or an unknown layout; MIPX_EUNSUPPORTED for an image of 2^32 / 3 pixels
+ * or more (the kernel's byte offsets inside an image are 32-bit).  No workspace. */
+int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                       int32_t layout, void *stream);
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                    int32_t bands, double xscale, double yscale, int32_t extend, void *stream);
 int mipx_op_zoom(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,

@@ -4,7 +4,8 @@ rocprofv3 passes see that kernel alone.
 
     python scripts/op_bench.py reducev --w 1024 --h 1024 --b 4 --n 512 --s 1.3333333333333333
     python scripts/op_bench.py textmark --w 3840 --h 2160 --b 3 --n 64
-    ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark
+    python scripts/op_bench.py ycc420 --w 3840 --h 2160 --n 64
+    ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
 """
 import argparse
 import ctypes as C
@@ -80,9 +81,14 @@ def main():
     elif a.op == "watermark":   # an RGBA watermark image at (100, 100)
         ob = b if b in (2, 4) else b + 1
         mask = torch.randint(0, 256, (mh * mw * 4,), dtype=torch.uint8, device=dev)
+    in_img = w * h * b          # input bytes of one image
+    if a.op in ("ycc420", "ycc444"):   # packed JPEG planes in, RGB out
+        b = ob = 3
+        layout = 1 if a.op == "ycc420" else 0
+        in_img = lib.mipx_ycc_bytes(w, h, layout)
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
-    x = torch.randint(0, 256, (n * w * h * b,), dtype=torch.uint8, device=dev)
+    x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
     y = torch.empty((n * ow * oh * ob,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream(dev)
@@ -117,6 +123,8 @@ def main():
             return lib.mipx_op_text_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, margin, a.opacity, colour, sp)
         if a.op == "watermark":
             return lib.mipx_op_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, 4, 100, 100, a.opacity, sp)
+        if a.op in ("ycc420", "ycc444"):
+            return lib.mipx_op_ycc_to_rgb(X, Y, n, w, h, layout, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -144,7 +152,7 @@ def main():
             groups.append(e0.elapsed_time(e1) / a.iters)
         return sorted(groups)[len(groups) // 2]
 
-    alg = n * (w * h * b + ow * oh * ob)   # bytes = input + output
+    alg = n * (in_img + ow * oh * ob)   # bytes = input + output
     line = {"op": a.op, "w": w, "h": h, "b": b, "n": n, "s": a.s, "s2": s2, "out": [ow, oh, ob],
             "sampling": ["corner", "centre"][lib.mipx_reduce_sampling()]}
     if not a.ab:
