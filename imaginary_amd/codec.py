@@ -176,6 +176,168 @@ def decode_ycc(buf: bytes):
     return np.concatenate([full[:, :, 0].ravel(), cb.ravel(), cr.ravel()]), layout
 
 
+# ---- JPEG from quantised coefficients (the engine's MIPX_OP_JPEGC output) ----------------
+# The four Huffman tables of Annex K.3 as (code counts per length 1..16, symbols): what every
+# libjpeg encoder writes unless it optimises them.
+_HUFF_DC_LUM = (bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes(range(12)))
+_HUFF_DC_CHR = (bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]), bytes(range(12)))
+_HUFF_AC_LUM = (bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125]), bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738"
+    "393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5"
+    "a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"))
+_HUFF_AC_CHR = (bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119]), bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a353637"
+    "38393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3"
+    "a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+HUFFMAN_TABLES = {0x00: _HUFF_DC_LUM, 0x10: _HUFF_AC_LUM, 0x01: _HUFF_DC_CHR, 0x11: _HUFF_AC_CHR}   # by DHT Tc/Th byte
+
+# natural index of the k-th coefficient in zigzag order
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+          21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53,
+          60, 61, 54, 47, 55, 62, 63)
+
+_STD_QLUM = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+             14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_STD_QCHR = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+             47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+
+def jpeg_qtables(quality: int):
+    """jpeg_set_quality(quality, TRUE) over the Annex K tables: (lum, chr), natural order.  The
+    host twin of mipx_jpeg_qtables, so writing a file needs no engine."""
+    if not 1 <= quality <= 100:
+        raise ValueError(f"JPEG quality {quality} outside 1..100")
+    s = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple([min(max((q * s + 50) // 100, 1), 255) for q in t] for t in (_STD_QLUM, _STD_QCHR))
+
+
+def _huff_codes(table):
+    """symbol -> (code, length), canonical (Annex C)."""
+    counts, symbols = table
+    codes, code, k = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(counts[length - 1]):
+            codes[symbols[k]] = (code, length)
+            code += 1
+            k += 1
+        code <<= 1
+    return codes
+
+
+def _jpegc_geometry(w: int, h: int, layout: int):
+    """Per component (wb, hb, sampling factor), and the MCUs across and down."""
+    ywb, yhb = (w + 7) // 8, (h + 7) // 8
+    if layout == YCC_444:
+        return [(ywb, yhb, 1)] * 3, ywb, yhb
+    if layout != YCC_420:
+        raise ValueError(f"unknown coefficient layout {layout}")
+    cwb, chb = ((w + 1) // 2 + 7) // 8, ((h + 1) // 2 + 7) // 8
+    return [(ywb, yhb, 2), (cwb, chb, 1), (cwb, chb, 1)], cwb, chb
+
+
+def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes:
+    """A baseline JFIF file from the engine's quantised coefficients (MIPX_OP_JPEGC: int16,
+    Y then Cb then Cr, real blocks in raster order, natural order inside a block), made at
+    `quality` in `layout` (YCC_444 / YCC_420).  Stand-in for libjpeg's jpeg_write_coefficients:
+    the Annex K Huffman tables, one interleaved scan, and libjpeg's dummy blocks where the
+    real blocks do not fill whole MCUs (zero AC; DC copied from the block to the left, or,
+    in a wholly dummy block row, from the last block of the same MCU's row above)."""
+    comps, mw, mh = _jpegc_geometry(w, h, layout)
+    c = np.ascontiguousarray(coefs).view(np.int16).ravel() if np.asarray(coefs).dtype == np.uint8 \
+        else np.asarray(coefs, dtype=np.int16).ravel()
+    if c.size != 64 * sum(wb * hb for wb, hb, _ in comps):
+        raise ValueError(f"{c.size} coefficients for {w}x{h} layout {layout}")
+    planes, at = [], 0
+    for wb, hb, s in comps:       # pad every component to whole MCUs with the dummy blocks
+        full = np.zeros((mh * s, mw * s, 64), np.int16)
+        full[:hb, :wb] = c[at:at + 64 * wb * hb].reshape(hb, wb, 64)
+        at += 64 * wb * hb
+        for x in range(wb, mw * s):
+            full[:hb, x, 0] = full[:hb, x - 1, 0]
+        for y in range(hb, mh * s):
+            for m in range(mw):
+                full[y, m * s:(m + 1) * s, 0] = full[y - 1, m * s + s - 1, 0]
+        planes.append(full[:, :, list(ZIGZAG)].astype(np.int32))
+    lum, chrom = jpeg_qtables(quality)
+
+    def seg(marker, body):
+        return bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + body
+
+    out = bytearray(b"\xff\xd8")
+    out += seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for i, t in enumerate((lum, chrom)):
+        out += seg(0xDB, bytes([i]) + bytes(t[k] for k in ZIGZAG))
+    sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3])
+    for i, (_, _, s) in enumerate(comps):
+        sof += bytes([i + 1, (s << 4) | s, 0 if i == 0 else 1])
+    out += seg(0xC0, sof)
+    for tc in (0x00, 0x10, 0x01, 0x11):
+        out += seg(0xC4, bytes([tc]) + HUFFMAN_TABLES[tc][0] + HUFFMAN_TABLES[tc][1])
+    out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+
+    dc_codes = [_huff_codes(_HUFF_DC_LUM), _huff_codes(_HUFF_DC_CHR)]
+    ac_codes = [_huff_codes(_HUFF_AC_LUM), _huff_codes(_HUFF_AC_CHR)]
+    acc, nbits = 0, 0            # the bit buffer, as one growing integer per MCU row
+    scan = bytearray()
+    pred = [0, 0, 0]
+
+    def put(code, length):
+        nonlocal acc, nbits
+        acc = (acc << length) | code
+        nbits += length
+
+    def put_value(v, size):      # the `size` low bits of v, or of v - 1 when negative
+        put((v if v >= 0 else v - 1) & ((1 << size) - 1), size)
+
+    def flush(final=False):
+        nonlocal acc, nbits
+        if final and nbits % 8:
+            pad = 8 - nbits % 8
+            acc = (acc << pad) | ((1 << pad) - 1)
+            nbits += pad
+        whole = nbits // 8
+        if whole:
+            rest = nbits - 8 * whole
+            scan.extend((acc >> rest).to_bytes(whole, "big").replace(b"\xff", b"\xff\x00"))
+            acc &= (1 << rest) - 1
+            nbits = rest
+
+    for my in range(mh):
+        for mx in range(mw):
+            for ci, (_, _, s) in enumerate(comps):
+                t = 0 if ci == 0 else 1
+                for by in range(s):
+                    for bx in range(s):
+                        blk = planes[ci][my * s + by, mx * s + bx]
+                        d = int(blk[0]) - pred[ci]
+                        pred[ci] = int(blk[0])
+                        size = abs(d).bit_length()
+                        put(*dc_codes[t][size])
+                        if size:
+                            put_value(d, size)
+                        run = 0
+                        nz = np.flatnonzero(blk[1:]) + 1
+                        prev = 0
+                        for k in nz.tolist():
+                            run = k - prev - 1
+                            while run > 15:
+                                put(*ac_codes[t][0xF0])
+                                run -= 16
+                            v = int(blk[k])
+                            size = abs(v).bit_length()
+                            put(*ac_codes[t][(run << 4) | size])
+                            put_value(v, size)
+                            prev = k
+                        if prev != 63:
+                            put(*ac_codes[t][0x00])
+        flush()
+    flush(final=True)
+    out += scan
+    out += b"\xff\xd9"
+    return bytes(out)
+
+
 _SANS_FACES = ("DejaVuSans.ttf", "LiberationSans-Regular.ttf", "NotoSans-Regular.ttf", "FreeSans.ttf", "Arial.ttf")
 DEFAULT_FONT_POINTS = 10.0
 

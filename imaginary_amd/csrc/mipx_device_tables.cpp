@@ -20,7 +20,7 @@ namespace mipx {
 namespace {
 
 enum Kind {
-    kReduce, kPairs, kI8, kI8s, kI8sFold, kVPlan, kHops, kBlurOps, kGauss, kColour, kBicubic, kBlob, kEnlmAxis, kKinds
+    kReduce, kPairs, kI8, kI8s, kI8sFold, kVPlan, kHops, kBlurOps, kGauss, kColour, kBicubic, kBlob, kEnlmAxis, kJpegc, kKinds
 };
 
 // The parameters a table was built from.  Fixed-size kinds leave `contents` empty (no heap
@@ -195,6 +195,10 @@ bool sep_spec_gauss(double sigma, double min_ampl, SepSpec *s) {
 const float *device_colour_tables() { return as<float>(fetch(key_of(kColour), build_colour_tables)); }
 
 const int *device_bicubic_table() { return as<int>(fetch(key_of(kBicubic), build_bicubic_table)); }
+
+const uint32_t *device_jpegc_recips(int quality) {
+    return as<uint32_t>(fetch(key_of(kJpegc, 0, quality), [&] { return build_jpegc_recips(quality); }));
+}
 
 // Small host-built constant tables (per-lane MFMA operands and the like) copied to the
 // current device once, keyed by their contents.

@@ -98,6 +98,7 @@ const uint8_t *device_rcol_hops(double hs, int bands, bool centre, int ox0, int 
 const signed char *device_blur_ops(const std::vector<int> &mask, int bands, int delta, int nks, int vperm);
 const float *device_colour_tables();  // [256 v2y | kQuantElements cbrt | 257 y2v]
 const int *device_bicubic_table();     // 129 x 4
+const uint32_t *device_jpegc_recips(int quality);  // k_jpegc: [lum 64 | chr 64] reciprocals of the quality's tables
 // float copy of the integer gaussmat mask; *scale = mask sum
 const float *device_gauss_table(double sigma, double min_ampl, int *n_taps, int *scale);
 // `bytes` of host data on the current device, cached by contents (small constant tables)
@@ -199,6 +200,8 @@ int textmark_launch(const uint8_t *in, const uint8_t *mask, uint8_t *out, int n,
                     int th, int margin, float opacity, const int *colour, hipStream_t st);
 // k_ycc.hip: packed JPEG planes (MIPX_YCC_*) -> RGB
 int ycc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, hipStream_t st);
+// k_jpegc.hip: RGB -> the quantised DCT coefficients of a JPEG (MIPX_YCC_* layout, quality 1..100)
+int jpegc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, int quality, hipStream_t st);
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,
@@ -211,6 +214,9 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
 // mipx_planner.cpp: bytes per image of the plan's input buffer: w * h * bands, or the packed
 // planes when step 0 is MIPX_OP_YCC (header fields already validated)
 size_t plan_input_bytes(const mipx_plan *p);
+// bytes per image of the plan's output buffer: out_w * out_h * out_bands, or the coefficients
+// when the last step is MIPX_OP_JPEGC (plan already validated)
+size_t plan_output_bytes(const mipx_plan *p);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

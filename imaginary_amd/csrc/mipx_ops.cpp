@@ -145,6 +145,14 @@ int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w
     return ycc_launch(d_in, d_out, n, w, h, layout, as_stream(stream));
 }
 
+int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
+                         int32_t quality, void *stream) {
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
+        quality < 1 || quality > 100)
+        return MIPX_EINVAL;
+    return jpegc_launch(d_in, d_out, n, w, h, layout, quality, as_stream(stream));
+}
+
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t bands, double xscale,
                    double yscale, int32_t extend, void *stream) {
     if (!d_in || !d_out || !geom_ok(n, w, h, bands) || !(xscale > 0) || !(yscale > 0)) return MIPX_EINVAL;

@@ -543,6 +543,7 @@ namespace {
 
 int textmark_index(const mipx_plan *p) {
     int i = p->n_steps;
+    if (i > 0 && p->steps[i - 1].op == MIPX_OP_JPEGC) --i;  // the coefficients are made of the marked image
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_BW) --i;
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_FLATTEN) --i;
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_WATERMARK) --i;
@@ -645,6 +646,52 @@ extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
     return MIPX_OK;
 }
 
+// ---- JPEG coefficient output (MIPX_OP_JPEGC) ---------------------------------------
+extern "C" size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout) {
+    if (w <= 0 || h <= 0 || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return 0;
+    const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
+    if (layout == MIPX_YCC_444) return 128 * 3 * ywb * yhb;
+    const size_t cwb = ((static_cast<size_t>(w) + 1) / 2 + 7) / 8, chb = ((static_cast<size_t>(h) + 1) / 2 + 7) / 8;
+    return 128 * (ywb * yhb + 2 * cwb * chb);
+}
+
+size_t mipx::plan_output_bytes(const mipx_plan *p) {
+    if (p->n_steps > 0 && p->steps[p->n_steps - 1].op == MIPX_OP_JPEGC)
+        return mipx_jpegc_bytes(p->out_w, p->out_h, p->steps[p->n_steps - 1].a[0]);
+    return static_cast<size_t>(p->out_w) * p->out_h * p->out_bands;
+}
+
+extern "C" int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]) {
+    return mipx::jpeg_qtables(quality, lum, chr) ? MIPX_OK : MIPX_EINVAL;
+}
+
+extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32_t quality) {
+    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (quality < 1 || quality > 100) {
+        mipx::set_error("mipx_plan_set_jpegc_output: quality %d outside 1..100", quality);
+        return MIPX_EINVAL;
+    }
+    if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
+        mipx::set_error("mipx_plan_set_jpegc_output: the plan makes %dx%dx%d, the coefficients are of 3 bands",
+                        plan->out_w, plan->out_h, plan->out_bands);
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps > 0 && plan->steps[plan->n_steps - 1].op == MIPX_OP_JPEGC) {
+        mipx::set_error("mipx_plan_set_jpegc_output: the plan already gives coefficients");
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps >= MIPX_MAX_STEPS) {
+        mipx::set_error("mipx_plan_set_jpegc_output: the plan is full (MIPX_MAX_STEPS)");
+        return MIPX_EINVAL;
+    }
+    mipx_step &s = plan->steps[plan->n_steps++];
+    std::memset(&s, 0, sizeof(s));
+    s.op = MIPX_OP_JPEGC;
+    s.a[0] = layout, s.a[1] = quality;
+    s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
+    return MIPX_OK;
+}
+
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {
     if (!stages || !out || n_stages <= 0) return MIPX_EINVAL;
     mipx_plan m{};
@@ -668,6 +715,10 @@ extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_p
             wm |= s.steps[i].op == MIPX_OP_WATERMARK || s.steps[i].op == MIPX_OP_TEXTMARK;
             if (k > 0 && s.steps[i].op == MIPX_OP_YCC) {  // only the request's input can be planes
                 mipx::set_error("mipx_plan_chain: stage %d takes planar input; only stage 0 may", k);
+                return MIPX_EINVAL;
+            }
+            if (k + 1 < n_stages && s.steps[i].op == MIPX_OP_JPEGC) {  // only the request's output can be coefficients
+                mipx::set_error("mipx_plan_chain: stage %d gives coefficients; only the last stage may", k);
                 return MIPX_EINVAL;
             }
         }

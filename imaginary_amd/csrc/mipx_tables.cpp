@@ -349,4 +349,37 @@ HostTable build_bicubic_table() {
     return r;
 }
 
+// jcparam.c: the Annex K.1 / K.2 tables (natural order) scaled by jpeg_quality_scaling and
+// clamped to 1..255 (force_baseline)
+bool jpeg_qtables(int quality, uint8_t lum[64], uint8_t chr[64]) {
+    static const uint8_t std_lum[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                                        14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                                        18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                        49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+    static const uint8_t std_chr[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+                                        24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                        99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                        99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+    if (quality < 1 || quality > 100 || !lum || !chr) return false;
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int k = 0; k < 64; ++k) {
+        lum[k] = static_cast<uint8_t>(std::min(std::max((std_lum[k] * s + 50) / 100, 1), 255));
+        chr[k] = static_cast<uint8_t>(std::min(std::max((std_chr[k] * s + 50) / 100, 1), 255));
+    }
+    return true;
+}
+
+HostTable build_jpegc_recips(int quality) {
+    uint8_t q[128];
+    if (!jpeg_qtables(quality, q, q + 64)) return {};
+    std::vector<uint32_t> t(128);
+    for (int k = 0; k < 128; ++k) {
+        const uint32_t m = ((1u << kJpegcRecipShift) + q[k] - 1u) / q[k];
+        t[k] = m | static_cast<uint32_t>(q[k]) << 21;
+    }
+    HostTable r;
+    r.bytes = as_bytes(t);
+    return r;
+}
+
 }  // namespace mipx

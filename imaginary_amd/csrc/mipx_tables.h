@@ -40,6 +40,11 @@ constexpr int kRsTabPad = 128;  // k_rmf4 stride-B tap rows: zero bytes in front
 constexpr int kRsTabW = 272;    // bytes per (phase, hi / lo) row: pad + 2 K steps + a fragment (70 KB per table)
 constexpr int kRcolPlanRow = 144;                              // k_rcol's vertical plan: bytes per output row
 constexpr int kRcolHopRec(int nks) { return 32 * nks + 16; }   // k_rcol's horizontal operands: bytes per lane record
+constexpr int kJpegcRecipShift = 20;                            // k_jpegc's reciprocals: m = ceil(2^20 / q)
+
+// ---- JPEG quantisation tables (libjpeg jpeg_set_quality(quality, TRUE) over Annex K) ------
+// natural (row-major) order; false for a quality outside 1..100
+bool jpeg_qtables(int quality, uint8_t lum[64], uint8_t chr[64]);
 
 // ---- host builders (mipx_tables.cpp) --------------------------------------------
 // What a builder returns: the table as it goes to the device, and what its fetcher reports
@@ -61,5 +66,9 @@ HostTable build_blur_ops(const std::vector<int> &mask, int bands, int delta, int
 HostTable build_gauss_table(double sigma, double min_ampl);        // meta: taps, scale
 HostTable build_colour_tables();
 HostTable build_bicubic_table();
+// k_jpegc's quantisation divisors at one quality: [lum 64 | chr 64] uint32 in natural order, each
+// m | q << 21 with m = ceil(2^kJpegcRecipShift / q): (n * m) >> kJpegcRecipShift == n / q for
+// every n < 2^12, so ((c + 4 q) >> 3) through it is (c + 4 q) / (8 q) for c + 4 q < 2^15
+HostTable build_jpegc_recips(int quality);
 
 }  // namespace mipx

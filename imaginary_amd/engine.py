@@ -11,11 +11,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, YCC_444, YCC_420, sync_tuning)
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, YCC_444, YCC_420, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
            "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420",
+           "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -294,6 +295,33 @@ def _planes(plan: MipxPlan, planes) -> np.ndarray:
     return x
 
 
+def jpegc_bytes(w: int, h: int, layout: int) -> int:
+    """mipx_jpegc_bytes: bytes of one image's JPEG coefficients (0 for bad arguments)."""
+    return int(lib.mipx_jpegc_bytes(w, h, layout))
+
+
+def jpeg_qtables(quality: int):
+    """mipx_jpeg_qtables: (lum, chr), 64 uint8 each in natural order, of jpeg_set_quality."""
+    lum, chrom = np.empty(64, np.uint8), np.empty(64, np.uint8)
+    check(lib.mipx_jpeg_qtables(quality, lum.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                chrom.ctypes.data_as(C.POINTER(C.c_uint8))), "mipx_jpeg_qtables")
+    return lum, chrom
+
+
+def plan_set_jpegc_output(plan: MipxPlan, layout: int, quality: int) -> MipxPlan:
+    """mipx_plan_set_jpegc_output on `plan` (in place; returned for convenience): the plan then
+    gives the quantised DCT coefficients of its 3-band result (YCC_444 or YCC_420, made at
+    `quality`) instead of RGB pixels."""
+    check(lib.mipx_plan_set_jpegc_output(C.byref(plan), layout, quality), "mipx_plan_set_jpegc_output")
+    return plan
+
+
+def _jpegc_layout(plan: MipxPlan):
+    """The layout of the coefficients a plan gives, or None for interleaved pixels."""
+    last = plan.steps[plan.n_steps - 1] if plan.n_steps > 0 else None
+    return last.a[0] if last is not None and last.op == OP_JPEGC else None
+
+
 def fit_dimension(iw, ih, fw, fh):
     a, b = C.c_int32(), C.c_int32()
     check(lib.mipx_fit_dimension(iw, ih, fw, fh, C.byref(a), C.byref(b)), "mipx_fit_dimension")
@@ -346,15 +374,20 @@ class Engine:
         elif not (img.dtype == np.uint8 and img.ndim == 3 and img.strides[2] == 1
                   and img.strides[1] == img.shape[2]):
             img = np.ascontiguousarray(img, dtype=np.uint8)  # rows may keep a wider stride
-        shape = (plan.out_h, plan.out_w, plan.out_bands)
+        coefs = _jpegc_layout(plan)
+        if coefs is not None:  # the coefficients of one image, described as the plan's w x h x 3
+            shape, dtype = (jpegc_bytes(plan.out_w, plan.out_h, coefs) // 2,), np.int16
+        else:
+            shape, dtype = (plan.out_h, plan.out_w, plan.out_bands), np.uint8
         if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be contiguous uint8 {shape}")
+            out = np.empty(shape, dtype)
+        elif out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError(f"out must be contiguous {np.dtype(dtype).name} {shape}")
         ti = C.c_uint64()
         wmi = C.byref(_img(np.ascontiguousarray(wm, dtype=np.uint8))) if wm is not None else None
         src = MipxImg(img.ctypes.data, plan.in_w, plan.in_h, 3, 0) if planar else _img(img)
-        check(lib.mipx_submit(device, C.byref(plan), C.byref(src), wmi, C.byref(_img(out)),
+        dst = MipxImg(out.ctypes.data, plan.out_w, plan.out_h, 3, 0) if coefs is not None else _img(out)
+        check(lib.mipx_submit(device, C.byref(plan), C.byref(src), wmi, C.byref(dst),
                               C.byref(ti)), "mipx_submit")
         return ti.value, out
 
@@ -514,6 +547,24 @@ def ycc_to_rgb(planes: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
     return dout.download((n, h, w, 3))
 
 
+def rgb_to_jpegc(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
+    """mipx_op_rgb_to_jpegc on (h, w, 3) or (n, h, w, 3) uint8; returns the coefficients,
+    (n, jpegc_bytes / 2) int16."""
+    sync_tuning()
+    x = _batch(imgs)
+    n, h, w, b = x.shape
+    need = jpegc_bytes(w, h, layout)
+    if b != 3 or need == 0:
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
+    what = "mipx_op_rgb_to_jpegc"
+    din = _dev("in", what, x.nbytes, w * 3, x)
+    dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
+    check(lib.mipx_op_rgb_to_jpegc(din.ptr, dout.ptr, n, w, h, layout, quality, None), what)
+    synchronize()
+    _check_guards(what, din, dout)
+    return dout.download((n, need // 2), np.int16)
+
+
 def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
     sync_tuning()
     x = _batch(imgs)
@@ -532,7 +583,8 @@ def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
 def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
             junk: Optional[int] = None) -> np.ndarray:
     """mipx_execute_dev on a batch of host images (uploads, runs the plan, downloads); for a
-    plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes).
+    plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes);
+    a plan that gives coefficients (plan_set_jpegc_output) returns (n, jpegc_bytes / 2) int16.
     junk: fill the workspace (the ping-pong intermediates) and the output with this byte
     first, so a step that reads outside what the steps before it wrote shows up."""
     sync_tuning()
@@ -541,7 +593,9 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
     n = x.shape[0]
     what = "mipx_execute_dev"
     din = _dev("in", what, x.nbytes, plan.in_w if planar else x.shape[2] * x.shape[3], x)
-    dout = _dev("out", what, n * plan.out_w * plan.out_h * plan.out_bands, plan.out_w * plan.out_bands)
+    coefs = _jpegc_layout(plan)
+    out1 = jpegc_bytes(plan.out_w, plan.out_h, coefs) if coefs is not None else plan.out_w * plan.out_h * plan.out_bands
+    dout = _dev("out", what, n * out1, plan.out_w * plan.out_bands)
     wsb = lib.mipx_workspace_bytes(C.byref(plan), n)
     ws = _dev("ws", what, wsb) if wsb else None
     if junk is not None:
@@ -556,6 +610,8 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
                                ws.ptr if ws else None, wsb, None), what)
     synchronize()
     _check_guards(what, din, dout, dwm, ws)
+    if coefs is not None:
+        return dout.download((n, out1 // 2), np.int16)
     return dout.download((n, plan.out_h, plan.out_w, plan.out_bands))
 
 

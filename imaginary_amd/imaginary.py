@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _abi, codec
 from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_textmark, plan_chain, plan_make,
-                     plan_set_ycc_input, plan_textmark_geometry)
+                     plan_set_jpegc_output, plan_set_ycc_input, plan_textmark_geometry)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -479,8 +479,19 @@ def _add_textmark(plan, t: TextMark) -> np.ndarray:
     return mask[:, :, None]
 
 
+@dataclass
+class JpegCoefs:
+    """What process(..., jpeg_quality=q) returns in place of pixels: the quantised DCT
+    coefficients of the w x h result (codec.encode_jpeg_coefs writes the file)."""
+    coefs: np.ndarray
+    w: int
+    h: int
+    layout: int
+    quality: int
+
+
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
-            text: Optional[TextMark] = None, ycc: Optional[tuple] = None):
+            text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -493,7 +504,10 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     With `text`, the plan gets a text watermark step and the rendered mask takes the
     watermark slot.
     With `ycc` = (planes, layout) (codec.decode_ycc), a Decoded input's pixels are only a
-    shape: the plan takes the JPEG's packed planes and the engine upsamples and converts."""
+    shape: the plan takes the JPEG's packed planes and the engine upsamples and converts.
+    With `jpeg_quality` (1..100) and a 3-band result, the plan ends with the coefficient step
+    (4:2:0 below Q 90, 4:4:4 from Q 90, as codec.encode samples) and a JpegCoefs is returned;
+    results of other band counts come back as pixels."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         return process_bytes(bytes(img), opts, wm, text)
     opts = {k: v for k, v in opts.items() if k not in _ENCODE_ONLY}
@@ -523,6 +537,10 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
         if chain is not None:
             chain.append((plan, px, wm))
             return _placeholder(plan.out_h, plan.out_w, plan.out_bands)
+        if jpeg_quality is not None and plan.out_bands == 3:
+            layout = codec.YCC_444 if jpeg_quality >= 90 else codec.YCC_420
+            plan_set_jpegc_output(plan, layout, jpeg_quality)
+            return JpegCoefs(_run(plan, px, wm), plan.out_w, plan.out_h, layout, jpeg_quality)
         return _run(plan, px, wm)
     except _abi.MipxError as e:
         if e.code == _abi.MIPX_EUNSUPPORTED:
@@ -531,13 +549,16 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 
 
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
-                  ycc: bool = False) -> Image:
+                  ycc: bool = False, jpeg_coefs: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
     ycc: hand a 4:4:4 or 4:2:0 YCbCr JPEG to the engine as its planes (codec.decode_ycc), half
     the upload of RGB for 4:2:0, when the request decodes at full size; the bytes are the
-    same either way.  Shrink-on-load requests and every other file keep the RGB decode."""
+    same either way.  Shrink-on-load requests and every other file keep the RGB decode.
+    jpeg_coefs: when the answer is a JPEG of a 3-band image, let the engine run the encoder's
+    colour conversion, downsampling, DCT and quantisation too and only entropy-code on the host
+    (codec.encode_jpeg_coefs); the scan is the same either way.  Other outputs keep the RGB path."""
     opts = dict(opts)
     out_type = str(opts.pop("type", "") or "")
     quality = int(opts.pop("quality", 0) or 0)
@@ -552,6 +573,9 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         return codec.decode(buf, s)
 
     itype = hdr.type if hdr.type in _abi.TYPES else "unknown"
+    t = out_type or (hdr.type if hdr.type in ("jpeg", "png", "webp", "gif", "tiff") else "png")
+    q = quality or codec.DEFAULT_QUALITY
+    jq = q if jpeg_coefs and t == "jpeg" and 1 <= q <= 100 else None   # process() looks at the bands
     if wm_px is not None:
         opts = dict(opts, wm_enable=1)
     # plan on the header first: the decode depends on the plan's shrink-on-load
@@ -569,15 +593,18 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text)
     elif plan.load_shrink > 1:  # process() re-plans on the codec-shrunk size
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
-        px = process(src, opts, wm=wm_px, redecode=redecode, text=text)
+        px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq)
     else:
         planes = codec.decode_ycc(buf) if ycc and hdr.bands == 3 else None
         if planes is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         ycc=planes)
+                         ycc=planes, jpeg_quality=jq)
         else:
-            px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text)
-    t = out_type or (hdr.type if hdr.type in ("jpeg", "png", "webp", "gif", "tiff") else "png")
+            px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text,
+                         jpeg_quality=jq)
+    if isinstance(px, JpegCoefs):
+        body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)
+        return Image(body, codec.mime_type(codec.sniff_type(body)))
     try:
         body = codec.encode(px, t, quality or None, compression)
     except codec.CodecError as e:

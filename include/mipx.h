@@ -38,6 +38,8 @@
  *    aligned input and output pointers only and return MIPX_EINVAL for others.
  *    A plan that starts with MIPX_OP_YCC, and mipx_op_ycc_to_rgb, read n * mipx_ycc_bytes()
  *    input bytes instead (packed JPEG planes, see MIPX_YCC_*), at any alignment.
+ *    A plan that ends with MIPX_OP_JPEGC, and mipx_op_rgb_to_jpegc, write n * mipx_jpegc_bytes()
+ *    output bytes instead (JPEG coefficients), at any alignment.
  *  - Thread-safe: mipx_submit / mipx_wait / mipx_process may be called from
  *    many threads (one goroutine per HTTP request).
  */
@@ -129,9 +131,14 @@ enum {
     MIPX_OP_TEXTMARK,    /* a[0..1] = mask w, h; a[2] = margin; a[3..5] = colour; d[0] = opacity after
                             defaulting; out_bands = 3; the rendered text mask travels as the request's
                             watermark image (a[0] x a[1] x 1)              (bimg vips_watermark) */
-    MIPX_OP_YCC          /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, whose input
+    MIPX_OP_YCC,         /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, whose input
                             buffer is then the packed planes (mipx_plan_set_ycc_input)
                                                      (libjpeg upsample + colour conversion) */
+    MIPX_OP_JPEGC        /* a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/out_bands = the image it
+                            consumes (w, h, 3); only as the LAST step of a plan whose image there has 3
+                            bands; the output buffer is then the quantised coefficients
+                            (mipx_plan_set_jpegc_output)
+                                  (libjpeg colour conversion, downsample, forward DCT, quantisation) */
 };
 
 /* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
@@ -143,6 +150,17 @@ enum {
  * libjpeg's integer YCbCr -> RGB, bit for bit (PARITY_ASSUMPTIONS.md row 16). */
 enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
 
+/* JPEG coefficient output (MIPX_OP_JPEGC): what a JPEG encoder has in front of its entropy
+ * coder, so the host only Huffman-codes (libjpeg jpeg_write_coefficients).  The same two
+ * layouts name the file's sampling.  One image is the quantised DCT coefficients of the real
+ * blocks only, int16 little-endian: component Y, then Cb, then Cr; each component hb x wb
+ * blocks in raster order; each block 64 coefficients in natural (row-major) order, i.e.
+ * libjpeg's coefficient arrays.  Y (and 4:4:4 chroma): wb = ceil(w / 8), hb = ceil(h / 8).
+ * 4:2:0 chroma: wb = ceil(ceil(w / 2) / 8), hb = ceil(ceil(h / 2) / 8).  The blocks that pad a
+ * partial MCU in 4:2:0 (zero AC, DC copied) are the entropy coder's and are not emitted.  The
+ * engine computes libjpeg's integer RGB -> YCbCr, its h2v2 downsample, the "islow" forward DCT
+ * and the quantisation with the tables of jpeg_set_quality(quality, TRUE), bit for bit
+ * (PARITY_ASSUMPTIONS.md row 17); images and both pointers start on any byte. */
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
 typedef struct mipx_step {
     int32_t op;
@@ -227,6 +245,23 @@ int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t mask_h, int3
  * already starts with the step, or a full plan. */
 size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout);
 int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout);
+/* JPEG coefficient output (MIPX_OP_JPEGC, see MIPX_YCC_*).  The three calls work without a GPU.
+ * mipx_jpegc_bytes: bytes of one w x h image's coefficients, 128 * its real blocks; 0 for a
+ * non-positive size or an unknown layout.
+ * mipx_plan_set_jpegc_output: appends the MIPX_OP_JPEGC step to a plan whose output has 3
+ * bands.  The plan's geometry (in_*, out_w, out_h, out_bands) is unchanged; what changes is
+ * the output buffer, which is then mipx_jpegc_bytes(out_w, out_h, layout) bytes per image for
+ * mipx_execute_dev, and for mipx_submit a mipx_img of w = out_w, h = out_h, bands = 3,
+ * stride = 0 whose data has that many bytes (anything else is MIPX_EINVAL).  The step is
+ * legal only as a plan's last one; in a mipx_plan_chain it may appear in the last stage only.
+ * MIPX_EINVAL for an unknown layout, a quality outside 1..100, out_bands != 3, a plan that
+ * already ends with the step, or a full plan.
+ * mipx_jpeg_qtables: the quantisation tables the coefficients of `quality` were made with, 64
+ * values each in natural order (a DQT segment wants them in zigzag order); MIPX_EINVAL for
+ * a quality outside 1..100 or a NULL table. */
+size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout);
+int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32_t quality);
+int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
 /* imaginary image.go:190 calculateDestinationFitDimension */
 int mipx_fit_dimension(int32_t image_w, int32_t image_h, int32_t fit_w, int32_t fit_h,
                        int32_t *out_w, int32_t *out_h);
@@ -300,6 +335,13 @@ int mipx_op_text_watermark(const uint8_t *d_in, const uint8_t *d_mask, uint8_t *
  * or more (the kernel's byte offsets inside an image are 32-bit).  No workspace. */
 int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                        int32_t layout, void *stream);
+/* n x h x w x 3 RGB -> n images of JPEG coefficients (n * mipx_jpegc_bytes(w, h, layout) bytes);
+ * both pointers at any alignment.  MIPX_EINVAL, before any HIP call, for NULL pointers, n <= 0,
+ * a non-positive size, an unknown layout or a quality outside 1..100; MIPX_EUNSUPPORTED for an
+ * image whose input or output is 2^32 bytes or more (the kernel's byte offsets inside an image
+ * are 32-bit).  No workspace. */
+int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                         int32_t layout, int32_t quality, void *stream);
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                    int32_t bands, double xscale, double yscale, int32_t extend, void *stream);
 int mipx_op_zoom(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,

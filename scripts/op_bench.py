@@ -5,7 +5,9 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py reducev --w 1024 --h 1024 --b 4 --n 512 --s 1.3333333333333333
     python scripts/op_bench.py textmark --w 3840 --h 2160 --b 3 --n 64
     python scripts/op_bench.py ycc420 --w 3840 --h 2160 --n 64
+    python scripts/op_bench.py jpegc420 --w 3840 --h 2160 --n 64 --q 75
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
+         jpegc420 jpegc444
 """
 import argparse
 import ctypes as C
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--mh", type=int, default=0, help="textmark / watermark: mask or watermark height (0 = mw / 5)")
     ap.add_argument("--margin", type=int, default=-1, help="textmark: margin (-1 = the mask width, bimg's default)")
     ap.add_argument("--opacity", type=float, default=0.25)
+    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444: JPEG quality")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -86,10 +89,15 @@ def main():
         b = ob = 3
         layout = 1 if a.op == "ycc420" else 0
         in_img = lib.mipx_ycc_bytes(w, h, layout)
+    out_img = ow * oh * ob      # output bytes of one image
+    if a.op in ("jpegc420", "jpegc444"):   # RGB in, quantised DCT coefficients out
+        b = ob = 3              # "out" names the image the step consumes; its bytes are out_img
+        layout = 1 if a.op == "jpegc420" else 0
+        in_img, out_img = w * h * 3, lib.mipx_jpegc_bytes(w, h, layout)
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
-    y = torch.empty((n * ow * oh * ob,), dtype=torch.uint8, device=dev)
+    y = torch.empty((n * out_img,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream(dev)
     sp = C.c_void_p(st.cuda_stream)
@@ -125,6 +133,8 @@ def main():
             return lib.mipx_op_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, 4, 100, 100, a.opacity, sp)
         if a.op in ("ycc420", "ycc444"):
             return lib.mipx_op_ycc_to_rgb(X, Y, n, w, h, layout, sp)
+        if a.op in ("jpegc420", "jpegc444"):
+            return lib.mipx_op_rgb_to_jpegc(X, Y, n, w, h, layout, a.q, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -152,7 +162,7 @@ def main():
             groups.append(e0.elapsed_time(e1) / a.iters)
         return sorted(groups)[len(groups) // 2]
 
-    alg = n * (in_img + ow * oh * ob)   # bytes = input + output
+    alg = n * (in_img + out_img)   # bytes = input + output
     line = {"op": a.op, "w": w, "h": h, "b": b, "n": n, "s": a.s, "s2": s2, "out": [ow, oh, ob],
             "sampling": ["corner", "centre"][lib.mipx_reduce_sampling()]}
     if not a.ab:
