@@ -11,6 +11,7 @@ from .engine import (DeviceBuffer, Engine, GuardedBuffer, device_count, execute,
                      guard_damage, guard_setting, guarded_calls, make_input, make_opts, plan_add_textmark, plan_chain,
                      plan_make, plan_textmark_geometry, reduce_sampling, run_op, set_guard, set_reduce_sampling,
                      smartcrop_origins, synchronize, plan_set_ycc_input, ycc_bytes, ycc_to_rgb, YCC_444, YCC_420,
-                     plan_set_jpegc_output, jpegc_bytes, jpeg_qtables, rgb_to_jpegc)
+                     plan_set_jpegc_output, jpegc_bytes, jpeg_qtables, rgb_to_jpegc,
+                     plan_set_jpegd_input, jpegd_bytes, jpegd_to_rgb)
 
 __version__ = "0.2.0"

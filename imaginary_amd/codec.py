@@ -338,6 +338,218 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes
     return bytes(out)
 
 
+# ---- quantised coefficients from a JPEG (the engine's MIPX_OP_JPEGD input) -----------------
+JPEGD_HEADER_BYTES = 384   # MIPX_JPEGD_HEADER_BYTES: the tables of Y, Cb, Cr, 64 uint16 each
+
+
+def _huff_lookup(counts, symbols):
+    """A 65536-entry table over the next 16 bits of the stream: (code length << 8) | symbol,
+    0 where no code matches."""
+    lut = np.zeros(65536, np.int32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(counts[length - 1]):
+            if code >= 1 << length:
+                return None
+            lut[code << (16 - length):(code + 1) << (16 - length)] = (length << 8) | symbols[k]
+            code += 1
+            k += 1
+        code <<= 1
+    return lut.tolist()
+
+
+def _jpeg_segments(buf: bytes):
+    """What decode_jpeg_coefs needs of a file's headers, or None for a file it does not take:
+    (w, h, components [(id, h, v, tq, td, ta)], tables {tq: 64 natural-order values}, Huffman
+    lookups {Tc/Th byte: lookup}, restart interval, the entropy-coded intervals)."""
+    import re
+    if buf[:2] != b"\xff\xd8":
+        return None
+    p, n = 2, len(buf)
+    qt, huff, frame, restart = {}, {}, None, 0
+    jfif, adobe = False, None
+    while True:
+        while p < n and buf[p] == 0xFF and p + 1 < n and buf[p + 1] == 0xFF:
+            p += 1   # fill bytes
+        if p + 4 > n or buf[p] != 0xFF:
+            return None
+        m = buf[p + 1]
+        size = int.from_bytes(buf[p + 2:p + 4], "big")
+        body = buf[p + 4:p + 2 + size]
+        if size < 2 or len(body) != size - 2:
+            return None
+        p += 2 + size
+        if m == 0xE0 and body[:5] == b"JFIF\x00":
+            jfif = True
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDB:
+            while body:
+                if body[0] >> 4 or len(body) < 65:     # 16-bit tables
+                    return None
+                t = [0] * 64
+                for k in range(64):
+                    t[ZIGZAG[k]] = body[1 + k]
+                qt[body[0] & 15] = t
+                body = body[65:]
+        elif m == 0xC4:
+            while body:
+                if len(body) < 17:
+                    return None
+                cnt = sum(body[1:17])
+                if len(body) < 17 + cnt or cnt > 256:
+                    return None
+                huff[body[0]] = _huff_lookup(body[1:17], body[17:17 + cnt])
+                if huff[body[0]] is None:
+                    return None
+                body = body[17 + cnt:]
+        elif m in (0xC0, 0xC1):                         # baseline, extended sequential; Huffman
+            if frame is not None or len(body) < 6 or body[0] != 8 or body[5] != 3 or len(body) != 6 + 9:
+                return None
+            frame = (int.from_bytes(body[3:5], "big"), int.from_bytes(body[1:3], "big"),
+                     [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(3)])
+        elif m == 0xDD:
+            if len(body) != 2:
+                return None
+            restart = int.from_bytes(body, "big")
+        elif m == 0xDA:
+            break
+        elif 0xC0 <= m <= 0xCF or m in (0xDC, 0xD8, 0xD9):   # progressive, lossless, arithmetic, DNL, ...
+            return None
+    w, h, comps = frame if frame is not None else (0, 0, [])
+    if w <= 0 or h <= 0 or len(body) != 10 or body[0] != 3 or bytes(body[7:10]) != b"\x00\x3f\x00":
+        return None                                          # one interleaved scan of the whole spectrum
+    full = []
+    for i, (cid, ch, cv, tq) in enumerate(comps):
+        if body[1 + 2 * i] != cid or tq not in qt:
+            return None
+        td, ta = body[2 + 2 * i] >> 4, 0x10 | (body[2 + 2 * i] & 15)
+        if td not in huff or ta not in huff:
+            return None
+        full.append((cid, ch, cv, tq, td, ta))
+    # the colour space by the rules decode_ycc applies
+    if adobe == 0:                                           # Adobe marker, transform 0: the components are RGB
+        return None
+    if not jfif and adobe is None and [c[0] for c in full] == [82, 71, 66]:
+        return None   # no JFIF / Adobe marker and component ids 'R' 'G' 'B': libjpeg takes it as RGB
+    # the scan's bytes up to the next marker, cut at the restart markers
+    parts, at, end = [], p, None
+    for hit in re.finditer(rb"\xff[^\x00]", buf[p:]):
+        b1, q = hit.group()[1], p + hit.start()
+        if b1 == 0xFF:
+            return None                                      # fill bytes inside a scan: not worth the care
+        parts.append(buf[at:q])
+        at = q + 2
+        if not 0xD0 <= b1 <= 0xD7:
+            end = b1
+            break
+    if end != 0xD9:                                          # truncated, or another scan follows
+        return None
+    return w, h, full, qt, huff, restart, parts
+
+
+def decode_jpeg_coefs(buf: bytes):
+    """A JPEG's quantised DCT coefficients as its entropy decoder has them, packed for the
+    engine's MIPX_OP_JPEGD step: (payload, layout) with payload a 1-D uint8 array of the file's
+    quantisation tables (Y, Cb, Cr: 64 little-endian uint16 each, natural order) and then the
+    int16 coefficients of the real blocks only (Y, Cb, Cr; blocks in raster order; natural order
+    inside a block), or None (it never raises) for every file it does not take: anything but an
+    8-bit baseline or extended-sequential Huffman JPEG of 3 YCbCr components sampled 4:4:4 or
+    4:2:0 in one interleaved scan, so progressive, arithmetic-coded, grey, CMYK, RGB, 4:2:2 and
+    truncated files, and what is no JPEG at all (the caller then takes decode()).
+
+    Stand-in for libjpeg's jpeg_read_coefficients: a pure-Python Huffman decoder (any tables,
+    restart intervals) that looks codes up by the next 16 bits of the stream."""
+    try:
+        seg = _jpeg_segments(bytes(buf))
+        if seg is None:
+            return None
+        w, h, comps, qt, huff, restart, parts = seg
+        samp = [(c[1], c[2]) for c in comps]
+        layout = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}.get(tuple(samp))
+        if layout is None:
+            return None
+        geo, mw, mh = _jpegc_geometry(w, h, layout)
+        if restart == 0:
+            restart = mw * mh
+        if len(parts) != -(-mw * mh // restart):
+            return None
+        # a block is at least 2 bits (a DC code and an end-of-block): a header that promises more
+        # blocks than the scan can hold is damaged, and must not size the arrays below
+        if sum(s * s for _, _, s in geo) * mw * mh > 4 * sum(len(d) for d in parts):
+            return None
+        store = [[0] * (64 * mw * mh * s * s) for _, _, s in geo]
+        order = []      # the blocks of one MCU: (component, row in the MCU, column in the MCU)
+        for ci, (_, _, s) in enumerate(geo):
+            order += [(ci, by, bx) for by in range(s) for bx in range(s)]
+        dc = [huff[c[4]] for c in comps]
+        ac = [huff[c[5]] for c in comps]
+        zz = ZIGZAG
+        mcu = 0
+        for data in parts:
+            avail = 8 * len(data.replace(b"\xff\x00", b"\xff"))
+            data = data.replace(b"\xff\x00", b"\xff") + b"\x00" * 16
+            acc, nbits, pos = 0, 0, 0
+            pred = [0, 0, 0]
+            for mcu in range(mcu, min(mcu + restart, mw * mh)):
+                my, mx = divmod(mcu, mw)
+                for ci, by, bx in order:
+                    s = geo[ci][2]
+                    out = store[ci]
+                    base = 64 * ((my * s + by) * mw * s + mx * s + bx)
+                    lut = dc[ci]
+                    k = 0
+                    while k < 64:
+                        if nbits < 32:
+                            acc = ((acc & ((1 << nbits) - 1)) << 32) | int.from_bytes(data[pos:pos + 4], "big")
+                            pos += 4
+                            nbits += 32
+                        look = lut[(acc >> (nbits - 16)) & 0xFFFF]
+                        if look == 0:
+                            return None
+                        nbits -= look >> 8
+                        size = look & 15
+                        if k == 0:
+                            if look & 0xF0:
+                                return None
+                            lut = ac[ci]
+                        else:
+                            run = (look >> 4) & 15
+                            if size == 0:
+                                if run != 15:
+                                    break          # end of block
+                                k += 16
+                                continue
+                            k += run
+                            if k > 63:
+                                return None
+                        v = 0
+                        if size:
+                            v = (acc >> (nbits - size)) & ((1 << size) - 1)
+                            nbits -= size
+                            if v < 1 << (size - 1):
+                                v -= (1 << size) - 1
+                        if k == 0:
+                            v = pred[ci] = pred[ci] + v
+                        out[base + zz[k]] = v
+                        k += 1
+                if 8 * pos - nbits > avail:
+                    return None                    # ran past the interval's bytes
+            mcu += 1
+        if mcu != mw * mh:
+            return None
+        body = []
+        for (wb, hb, s), flat in zip(geo, store):
+            a = np.array(flat, dtype=np.int64).reshape(mh * s, mw * s, 64)[:hb, :wb]
+            if a.size and (a.min() < -32768 or a.max() > 32767):
+                return None
+            body.append(a.astype("<i2").ravel())
+        head = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel()
+        return np.concatenate([head.view(np.uint8), np.concatenate(body).view(np.uint8)]), layout
+    except Exception:  # noqa: BLE001 - whatever this decoder cannot read, the RGB decode reports
+        return None
+
+
 _SANS_FACES = ("DejaVuSans.ttf", "LiberationSans-Regular.ttf", "NotoSans-Regular.ttf", "FreeSans.ttf", "Arial.ttf")
 DEFAULT_FONT_POINTS = 10.0
 

@@ -202,6 +202,8 @@ int textmark_launch(const uint8_t *in, const uint8_t *mask, uint8_t *out, int n,
 int ycc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, hipStream_t st);
 // k_jpegc.hip: RGB -> the quantised DCT coefficients of a JPEG (MIPX_YCC_* layout, quality 1..100)
 int jpegc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, int quality, hipStream_t st);
+// k_jpegd.hip: quantisation tables + quantised coefficients (MIPX_OP_JPEGD) -> the packed planes ycc_launch takes
+int jpegd_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, hipStream_t st);
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,
@@ -212,7 +214,8 @@ int smartcrop_extract(const uint8_t *in, uint8_t *out, int n, int w, int h, int 
 size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, double p1);
 
 // mipx_planner.cpp: bytes per image of the plan's input buffer: w * h * bands, or the packed
-// planes when step 0 is MIPX_OP_YCC (header fields already validated)
+// planes when step 0 is MIPX_OP_YCC, the coefficient payload when it is MIPX_OP_JPEGD (header
+// fields already validated)
 size_t plan_input_bytes(const mipx_plan *p);
 // bytes per image of the plan's output buffer: out_w * out_h * out_bands, or the coefficients
 // when the last step is MIPX_OP_JPEGC (plan already validated)

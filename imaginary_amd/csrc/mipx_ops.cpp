@@ -21,6 +21,9 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
         }
         case MIPX_OP_BLUR: return align_up(static_cast<size_t>(n) * w * h * bands);
         case MIPX_OP_SMARTCROP: return smartcrop_workspace_bytes(n, w, h, bands);
+        // the decoded planes between the inverse DCT and the upsample + conversion, packed as
+        // mipx_ycc_bytes; sized by the 4:4:4 bound, which needs no layout
+        case MIPX_OP_JPEGD: return align_up(static_cast<size_t>(n) * w * h * 3);
         default: return 0;
     }
 }
@@ -151,6 +154,26 @@ int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
         quality < 1 || quality > 100)
         return MIPX_EINVAL;
     return jpegc_launch(d_in, d_out, n, w, h, layout, quality, as_stream(stream));
+}
+
+int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
+                         void *d_ws, size_t ws_bytes, void *stream) {
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
+        return MIPX_EINVAL;
+    // byte offsets inside an image are 32-bit in both kernels
+    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+        set_error("jpeg coefficients to rgb: image %dx%d too large (an image's bytes >= 2^32)", w, h);
+        return MIPX_EUNSUPPORTED;
+    }
+    if (!d_ws || ws_bytes < op_workspace_bytes(MIPX_OP_JPEGD, n, w, h, 3, 0, 0)) {
+        set_error("jpeg coefficients to rgb: workspace %zu < %zu bytes", ws_bytes,
+                  op_workspace_bytes(MIPX_OP_JPEGD, n, w, h, 3, 0, 0));
+        return MIPX_EINVAL;
+    }
+    uint8_t *planes = static_cast<uint8_t *>(d_ws);
+    const int e = jpegd_launch(d_in, planes, n, w, h, layout, as_stream(stream));
+    if (e) return e;
+    return ycc_launch(planes, d_out, n, w, h, layout, as_stream(stream));
 }
 
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t bands, double xscale,

@@ -619,6 +619,7 @@ extern "C" size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout) {
 
 size_t mipx::plan_input_bytes(const mipx_plan *p) {
     if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_YCC) return mipx_ycc_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
+    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_JPEGD) return mipx_jpegd_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
     return static_cast<size_t>(p->in_w) * p->in_h * p->in_bands;
 }
 
@@ -630,6 +631,10 @@ extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
     }
     if (plan->n_steps > 0 && plan->steps[0].op == MIPX_OP_YCC) {
         mipx::set_error("mipx_plan_set_ycc_input: the plan already takes planar input");
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps > 0 && plan->steps[0].op == MIPX_OP_JPEGD) {
+        mipx::set_error("mipx_plan_set_ycc_input: the plan already takes coefficient input");
         return MIPX_EINVAL;
     }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
@@ -692,6 +697,37 @@ extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32
     return MIPX_OK;
 }
 
+// ---- JPEG coefficient input (MIPX_OP_JPEGD) ----------------------------------------
+extern "C" size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout) {
+    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
+    return coefs ? MIPX_JPEGD_HEADER_BYTES + coefs : 0;
+}
+
+extern "C" int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout) {
+    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (plan->in_bands != 3) {
+        mipx::set_error("mipx_plan_set_jpegd_input: the plan takes %d bands, a YCbCr JPEG makes 3", plan->in_bands);
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_YCC || plan->steps[0].op == MIPX_OP_JPEGD)) {
+        mipx::set_error("mipx_plan_set_jpegd_input: the plan already takes %s input",
+                        plan->steps[0].op == MIPX_OP_YCC ? "planar" : "coefficient");
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps >= MIPX_MAX_STEPS) {
+        mipx::set_error("mipx_plan_set_jpegd_input: the plan is full (MIPX_MAX_STEPS)");
+        return MIPX_EINVAL;
+    }
+    for (int i = plan->n_steps; i > 0; --i) plan->steps[i] = plan->steps[i - 1];
+    ++plan->n_steps;
+    mipx_step &s = plan->steps[0];
+    std::memset(&s, 0, sizeof(s));
+    s.op = MIPX_OP_JPEGD;
+    s.a[0] = layout;
+    s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = 3;
+    return MIPX_OK;
+}
+
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {
     if (!stages || !out || n_stages <= 0) return MIPX_EINVAL;
     mipx_plan m{};
@@ -715,6 +751,10 @@ extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_p
             wm |= s.steps[i].op == MIPX_OP_WATERMARK || s.steps[i].op == MIPX_OP_TEXTMARK;
             if (k > 0 && s.steps[i].op == MIPX_OP_YCC) {  // only the request's input can be planes
                 mipx::set_error("mipx_plan_chain: stage %d takes planar input; only stage 0 may", k);
+                return MIPX_EINVAL;
+            }
+            if (k > 0 && s.steps[i].op == MIPX_OP_JPEGD) {  // ... or a file's coefficients
+                mipx::set_error("mipx_plan_chain: stage %d takes coefficient input; only stage 0 may", k);
                 return MIPX_EINVAL;
             }
             if (k + 1 < n_stages && s.steps[i].op == MIPX_OP_JPEGC) {  // only the request's output can be coefficients

@@ -11,12 +11,13 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, YCC_444, YCC_420, sync_tuning)
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, YCC_444, YCC_420, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
            "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420",
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
+           "plan_set_jpegd_input", "jpegd_bytes", "jpegd_to_rgb",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -284,15 +285,42 @@ def _ycc_layout(plan: MipxPlan):
     return plan.steps[0].a[0] if plan.n_steps > 0 and plan.steps[0].op == OP_YCC else None
 
 
+def _jpegd_layout(plan: MipxPlan):
+    """The layout of the coefficient payload a plan's input is, or None for anything else."""
+    return plan.steps[0].a[0] if plan.n_steps > 0 and plan.steps[0].op == OP_JPEGD else None
+
+
+def _packed_input(plan: MipxPlan) -> bool:
+    """Whether the plan's input is bytes per image (planes or a coefficient payload), not pixels."""
+    return _ycc_layout(plan) is not None or _jpegd_layout(plan) is not None
+
+
 def _planes(plan: MipxPlan, planes) -> np.ndarray:
-    """A YCC plan's input as (n, bytes) uint8, from (bytes,) or (n, bytes)."""
+    """A YCC or JPEGD plan's input as (n, bytes) uint8, from (bytes,) or (n, bytes)."""
     x = np.ascontiguousarray(planes, dtype=np.uint8)
     if x.ndim == 1:
         x = x[None]
-    need = ycc_bytes(plan.in_w, plan.in_h, _ycc_layout(plan))
+    if _jpegd_layout(plan) is not None:
+        need, what = jpegd_bytes(plan.in_w, plan.in_h, _jpegd_layout(plan)), "coefficient"
+    else:
+        need, what = ycc_bytes(plan.in_w, plan.in_h, _ycc_layout(plan)), "planar"
     if x.ndim != 2 or x.shape[1] != need:
-        raise ValueError(f"planar input of shape {np.shape(planes)}: the plan takes ({need},) or (n, {need}) uint8")
+        raise ValueError(f"{what} input of shape {np.shape(planes)}: the plan takes ({need},) or (n, {need}) uint8")
     return x
+
+
+def jpegd_bytes(w: int, h: int, layout: int) -> int:
+    """mipx_jpegd_bytes: bytes of one image's coefficient payload, the 384 bytes of quantisation
+    tables and jpegc_bytes of coefficients (0 for bad arguments)."""
+    return int(lib.mipx_jpegd_bytes(w, h, layout))
+
+
+def plan_set_jpegd_input(plan: MipxPlan, layout: int) -> MipxPlan:
+    """mipx_plan_set_jpegd_input on `plan` (in place; returned for convenience): the plan then
+    takes a JPEG's quantisation tables and quantised coefficients (codec.decode_jpeg_coefs;
+    YCC_444 or YCC_420) instead of RGB pixels."""
+    check(lib.mipx_plan_set_jpegd_input(C.byref(plan), layout), "mipx_plan_set_jpegd_input")
+    return plan
 
 
 def jpegc_bytes(w: int, h: int, layout: int) -> int:
@@ -366,11 +394,11 @@ class Engine:
         result: contiguous uint8 of the plan's output shape.  The MIPX_* kernel knobs are
         re-read in Engine(), run_op and execute, not per request: a reload
         must not race the queue workers' launches."""
-        planar = _ycc_layout(plan) is not None
-        if planar:  # the packed planes of one image, described as the plan's w x h x 3
+        planar = _packed_input(plan)
+        if planar:  # the packed planes or the payload of one image, described as the plan's w x h x 3
             img = _planes(plan, img)
             if img.shape[0] != 1:
-                raise ValueError("submit takes one image's planes")
+                raise ValueError("submit takes one image's planes or payload")
         elif not (img.dtype == np.uint8 and img.ndim == 3 and img.strides[2] == 1
                   and img.strides[1] == img.shape[2]):
             img = np.ascontiguousarray(img, dtype=np.uint8)  # rows may keep a wider stride
@@ -565,6 +593,27 @@ def rgb_to_jpegc(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
     return dout.download((n, need // 2), np.int16)
 
 
+def jpegd_to_rgb(payload: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
+    """mipx_op_jpegd_to_rgb on coefficient payloads, (bytes,) or (n, bytes) uint8; returns (n, h, w, 3)."""
+    sync_tuning()
+    x = np.ascontiguousarray(payload, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x[None]
+    need = jpegd_bytes(w, h, layout)
+    if x.ndim != 2 or need == 0 or x.shape[1] != need:
+        raise ValueError(f"payload of shape {np.shape(payload)} for {w}x{h} layout {layout}: {need} bytes per image")
+    n = x.shape[0]
+    what = "mipx_op_jpegd_to_rgb"
+    din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
+    dout = _dev("out", what, n * h * w * 3, w * 3)
+    wsb = lib.mipx_op_workspace_bytes(OP_JPEGD, n, w, h, 3, 0.0, 0.0)
+    ws = _dev("ws", what, wsb)
+    check(lib.mipx_op_jpegd_to_rgb(din.ptr, dout.ptr, n, w, h, layout, ws.ptr, wsb, None), what)
+    synchronize()
+    _check_guards(what, din, dout, ws)
+    return dout.download((n, h, w, 3))
+
+
 def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
     sync_tuning()
     x = _batch(imgs)
@@ -583,12 +632,13 @@ def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
 def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
             junk: Optional[int] = None) -> np.ndarray:
     """mipx_execute_dev on a batch of host images (uploads, runs the plan, downloads); for a
-    plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes);
+    plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes),
+    and for one that takes coefficient input (plan_set_jpegd_input), on payloads of the same shapes;
     a plan that gives coefficients (plan_set_jpegc_output) returns (n, jpegc_bytes / 2) int16.
     junk: fill the workspace (the ping-pong intermediates) and the output with this byte
     first, so a step that reads outside what the steps before it wrote shows up."""
     sync_tuning()
-    planar = _ycc_layout(plan) is not None
+    planar = _packed_input(plan)
     x = _planes(plan, imgs) if planar else _batch(imgs)
     n = x.shape[0]
     what = "mipx_execute_dev"

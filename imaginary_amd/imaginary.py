@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _abi, codec
 from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_textmark, plan_chain, plan_make,
-                     plan_set_jpegc_output, plan_set_ycc_input, plan_textmark_geometry)
+                     plan_set_jpegc_output, plan_set_jpegd_input, plan_set_ycc_input, plan_textmark_geometry)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -491,7 +491,8 @@ class JpegCoefs:
 
 
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
-            text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None):
+            text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None,
+            jpeg_dct: Optional[tuple] = None):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -505,6 +506,9 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     watermark slot.
     With `ycc` = (planes, layout) (codec.decode_ycc), a Decoded input's pixels are only a
     shape: the plan takes the JPEG's packed planes and the engine upsamples and converts.
+    With `jpeg_dct` = (payload, layout) (codec.decode_jpeg_coefs) likewise: the plan takes the
+    file's quantisation tables and coefficients and the engine runs the inverse DCT too; it
+    takes precedence over `ycc`.
     With `jpeg_quality` (1..100) and a 3-band result, the plan ends with the coefficient step
     (4:2:0 below Q 90, 4:4:4 from Q 90, as codec.encode samples) and a JpegCoefs is returned;
     results of other band counts come back as pixels."""
@@ -529,7 +533,12 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
             raise ImaginaryError("decoded size does not match the header", 500)
         if text is not None:
             wm = _add_textmark(plan, text)
-        if ycc is not None:
+        if jpeg_dct is not None:
+            if plan.load_shrink > 1 or chain is not None:
+                raise ImaginaryError("coefficient input needs the full-size decode of a single request", 500)
+            plan_set_jpegd_input(plan, jpeg_dct[1])
+            px = jpeg_dct[0]
+        elif ycc is not None:
             if plan.load_shrink > 1 or chain is not None:
                 raise ImaginaryError("planar input needs the full-size decode of a single request", 500)
             plan_set_ycc_input(plan, ycc[1])
@@ -549,7 +558,7 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 
 
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
-                  ycc: bool = False, jpeg_coefs: bool = False) -> Image:
+                  ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -558,7 +567,12 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     same either way.  Shrink-on-load requests and every other file keep the RGB decode.
     jpeg_coefs: when the answer is a JPEG of a 3-band image, let the engine run the encoder's
     colour conversion, downsampling, DCT and quantisation too and only entropy-code on the host
-    (codec.encode_jpeg_coefs); the scan is the same either way.  Other outputs keep the RGB path."""
+    (codec.encode_jpeg_coefs); the scan is the same either way.  Other outputs keep the RGB path.
+    jpeg_dct: hand a baseline 4:4:4 or 4:2:0 YCbCr JPEG to the engine as its quantisation tables and
+    quantised coefficients (codec.decode_jpeg_coefs), so the host only entropy-decodes, when the
+    request decodes at full size; the bytes are the same either way.  Shrink-on-load requests, the
+    rotate-and-re-encode path and every file that decoder declines keep today's path, which is
+    `ycc`'s when that is set too: of the two, jpeg_dct is tried first."""
     opts = dict(opts)
     out_type = str(opts.pop("type", "") or "")
     quality = int(opts.pop("quality", 0) or 0)
@@ -595,8 +609,12 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
         px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq)
     else:
-        planes = codec.decode_ycc(buf) if ycc and hdr.bands == 3 else None
-        if planes is not None:
+        dct = codec.decode_jpeg_coefs(buf) if jpeg_dct and hdr.bands == 3 and itype == "jpeg" else None
+        planes = codec.decode_ycc(buf) if dct is None and ycc and hdr.bands == 3 else None
+        if dct is not None:
+            px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
+                         jpeg_dct=dct, jpeg_quality=jq)
+        elif planes is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
                          ycc=planes, jpeg_quality=jq)
         else:

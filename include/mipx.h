@@ -40,6 +40,8 @@
  *    input bytes instead (packed JPEG planes, see MIPX_YCC_*), at any alignment.
  *    A plan that ends with MIPX_OP_JPEGC, and mipx_op_rgb_to_jpegc, write n * mipx_jpegc_bytes()
  *    output bytes instead (JPEG coefficients), at any alignment.
+ *    A plan that starts with MIPX_OP_JPEGD, and mipx_op_jpegd_to_rgb, read n * mipx_jpegd_bytes()
+ *    input bytes instead (quantisation tables + JPEG coefficients), at any alignment.
  *  - Thread-safe: mipx_submit / mipx_wait / mipx_process may be called from
  *    many threads (one goroutine per HTTP request).
  */
@@ -134,11 +136,15 @@ enum {
     MIPX_OP_YCC,         /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, whose input
                             buffer is then the packed planes (mipx_plan_set_ycc_input)
                                                      (libjpeg upsample + colour conversion) */
-    MIPX_OP_JPEGC        /* a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/out_bands = the image it
+    MIPX_OP_JPEGC,       /* a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/out_bands = the image it
                             consumes (w, h, 3); only as the LAST step of a plan whose image there has 3
                             bands; the output buffer is then the quantised coefficients
                             (mipx_plan_set_jpegc_output)
                                   (libjpeg colour conversion, downsample, forward DCT, quantisation) */
+    MIPX_OP_JPEGD        /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, never together
+                            with MIPX_OP_YCC; the input buffer is then the file's quantisation tables and
+                            quantised coefficients (mipx_plan_set_jpegd_input)
+                                  (libjpeg dequantisation, inverse DCT, upsample, colour conversion) */
 };
 
 /* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
@@ -161,6 +167,23 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * engine computes libjpeg's integer RGB -> YCbCr, its h2v2 downsample, the "islow" forward DCT
  * and the quantisation with the tables of jpeg_set_quality(quality, TRUE), bit for bit
  * (PARITY_ASSUMPTIONS.md row 17); images and both pointers start on any byte. */
+/* JPEG coefficient input (MIPX_OP_JPEGD): what a JPEG decoder has behind its entropy decoder
+ * (libjpeg jpeg_read_coefficients), so the host only Huffman-decodes.  One image is a 384-byte
+ * header followed by the coefficients.  The header is the file's quantisation tables of Y, Cb and
+ * Cr, each 64 little-endian uint16 values in natural (row-major) order, of which 1..255 are legal
+ * (8-bit tables); they travel with the image because they are the file's own, so requests with
+ * the same plan and different tables still batch.  The coefficients are exactly what
+ * MIPX_OP_JPEGC writes, mipx_jpegc_bytes(w, h, layout) bytes: int16 little-endian, the real
+ * blocks only (the shim drops the blocks that pad a partial MCU), Y then Cb then Cr, blocks in
+ * raster order, natural order inside a block.  The engine dequantises (the low 16 bits of
+ * coefficient * divisor, signed), runs libjpeg's "islow" inverse DCT (jidctint.c; pass 1 down the
+ * columns saturated to int16, pass 2 along the rows, + 128, clamped to 0..255) and then upsamples
+ * and converts as MIPX_OP_YCC does.  The result is libjpeg-turbo's for every file an encoder
+ * writes; where a sum saturates or wraps (corrupt or hand-made coefficients) it is the rule's,
+ * which tests/jpegd_ref.py restates, not the library's (PARITY_ASSUMPTIONS.md row 18).  Images
+ * and both pointers start on any byte. */
+#define MIPX_JPEGD_HEADER_BYTES 384
+
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
 typedef struct mipx_step {
     int32_t op;
@@ -262,6 +285,21 @@ int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout);
 size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout);
 int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32_t quality);
 int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
+/* JPEG coefficient input (MIPX_OP_JPEGD, see MIPX_JPEGD_HEADER_BYTES).  Both calls work without a GPU.
+ * mipx_jpegd_bytes: bytes of one w x h image's payload, 384 + mipx_jpegc_bytes(w, h, layout); 0
+ * for a non-positive size or an unknown layout.
+ * mipx_plan_set_jpegd_input: inserts the MIPX_OP_JPEGD step at index 0 of a 3-band plan (the
+ * other steps move up).  The plan's geometry is unchanged; what changes is the input buffer,
+ * which is then mipx_jpegd_bytes(in_w, in_h, layout) bytes per image for mipx_execute_dev, and
+ * for mipx_submit a mipx_img of w = in_w, h = in_h, bands = 3, stride = 0 whose data is the
+ * payload (anything else is MIPX_EINVAL).  Use it on plans with load_shrink 1.  In a
+ * mipx_plan_chain the step may appear in stage 0 only.  It composes with
+ * mipx_plan_add_textmark and mipx_plan_set_jpegc_output in either call order.  MIPX_EINVAL,
+ * with the plan untouched, for an unknown layout, in_bands != 3, a plan that already starts
+ * with this step or with MIPX_OP_YCC, or a full plan (mipx_plan_set_ycc_input likewise refuses
+ * a plan that starts with this step). */
+size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout);
+int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout);
 /* imaginary image.go:190 calculateDestinationFitDimension */
 int mipx_fit_dimension(int32_t image_w, int32_t image_h, int32_t fit_w, int32_t fit_h,
                        int32_t *out_w, int32_t *out_h);
@@ -342,6 +380,14 @@ int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w
  * are 32-bit).  No workspace. */
 int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                          int32_t layout, int32_t quality, void *stream);
+/* n payloads (n * mipx_jpegd_bytes(w, h, layout) bytes) -> n x h x w x 3 RGB; both pointers at any
+ * alignment.  The workspace takes the decoded planes between the two launches (inverse DCT, then
+ * the MIPX_OP_YCC kernels): mipx_op_workspace_bytes(MIPX_OP_JPEGD, n, w, h, 3, 0, 0) bytes.
+ * MIPX_EINVAL, before any HIP call, for NULL pointers, n <= 0, a non-positive size, an unknown
+ * layout or a workspace that is NULL or too small; MIPX_EUNSUPPORTED for an image whose payload
+ * or RGB is 2^32 bytes or more (the kernels' byte offsets inside an image are 32-bit). */
+int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                         int32_t layout, void *d_workspace, size_t workspace_bytes, void *stream);
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                    int32_t bands, double xscale, double yscale, int32_t extend, void *stream);
 int mipx_op_zoom(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,

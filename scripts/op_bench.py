@@ -6,8 +6,9 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py textmark --w 3840 --h 2160 --b 3 --n 64
     python scripts/op_bench.py ycc420 --w 3840 --h 2160 --n 64
     python scripts/op_bench.py jpegc420 --w 3840 --h 2160 --n 64 --q 75
+    python scripts/op_bench.py jpegd420 --w 3840 --h 2160 --n 64 --q 75
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
-         jpegc420 jpegc444
+         jpegc420 jpegc444 jpegd420 jpegd444
 """
 import argparse
 import ctypes as C
@@ -43,7 +44,7 @@ def main():
     ap.add_argument("--mh", type=int, default=0, help="textmark / watermark: mask or watermark height (0 = mw / 5)")
     ap.add_argument("--margin", type=int, default=-1, help="textmark: margin (-1 = the mask width, bimg's default)")
     ap.add_argument("--opacity", type=float, default=0.25)
-    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444: JPEG quality")
+    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444 / jpegd420 / jpegd444: JPEG quality")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -94,11 +95,33 @@ def main():
         b = ob = 3              # "out" names the image the step consumes; its bytes are out_img
         layout = 1 if a.op == "jpegc420" else 0
         in_img, out_img = w * h * 3, lib.mipx_jpegc_bytes(w, h, layout)
+    if a.op in ("jpegd420", "jpegd444"):   # quantisation tables + quantised DCT coefficients in, RGB out
+        b = ob = 3
+        layout = 1 if a.op == "jpegd420" else 0
+        in_img = lib.mipx_jpegd_bytes(w, h, layout)
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
     y = torch.empty((n * out_img,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
+    if a.op in ("jpegd420", "jpegd444"):
+        # what a decoder hands over: the coefficients the engine's own encoder makes of random pixels
+        # at --q (zero runs and small values, not noise), behind that quality's tables
+        import numpy as np
+        lum, chrom = (C.c_uint8 * 64)(), (C.c_uint8 * 64)()
+        assert lib.mipx_jpeg_qtables(a.q, lum, chrom) == 0
+        head = np.concatenate([np.array(t, dtype="<u2") for t in (lum, chrom, chrom)]).view(np.uint8)
+        px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
+        coefs = torch.empty((n * (in_img - 384),), dtype=torch.uint8, device=dev)
+        assert coefs.numel() == n * lib.mipx_jpegc_bytes(w, h, layout)
+        torch.cuda.synchronize(dev)
+        assert lib.mipx_op_rgb_to_jpegc(px.data_ptr(), coefs.data_ptr(), n, w, h, layout, a.q, None) == 0
+        check(lib.mipx_device_sync())
+        xv = x.view(n, in_img)
+        xv[:, 384:] = coefs.view(n, in_img - 384)
+        xv[:, :384] = torch.from_numpy(head).to(dev)
+        torch.cuda.synchronize(dev)
+        del px, coefs
     st = torch.cuda.current_stream(dev)
     sp = C.c_void_p(st.cuda_stream)
     X, Y, WS, WSB = x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel()
@@ -135,6 +158,8 @@ def main():
             return lib.mipx_op_ycc_to_rgb(X, Y, n, w, h, layout, sp)
         if a.op in ("jpegc420", "jpegc444"):
             return lib.mipx_op_rgb_to_jpegc(X, Y, n, w, h, layout, a.q, sp)
+        if a.op in ("jpegd420", "jpegd444"):
+            return lib.mipx_op_jpegd_to_rgb(X, Y, n, w, h, layout, WS, WSB, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
