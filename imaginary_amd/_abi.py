@@ -139,6 +139,7 @@ _SIG = {
     "mipx_jpeg_qtables": (C.c_int, [_I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "mipx_jpegd_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegd_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
+    "mipx_plan_set_jpegd_input_scaled": (C.c_int, [C.POINTER(MipxPlan), _I, _I, _I, _I]),
     "mipx_submit": (C.c_int, [C.c_int, C.POINTER(MipxPlan), C.POINTER(MipxImg), C.POINTER(MipxImg),
                               C.POINTER(MipxImg), C.POINTER(C.c_uint64)]),
     "mipx_wait": (C.c_int, [C.c_uint64, C.c_int]),
@@ -160,6 +161,7 @@ _SIG = {
     "mipx_op_ycc_to_rgb": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P]),
     "mipx_op_rgb_to_jpegc": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P]),
     "mipx_op_jpegd_to_rgb": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "mipx_op_jpegd_to_rgb_scaled": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_affine": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P]),
     "mipx_op_zoom": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _I, _P]),
     "mipx_op_flatten": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, C.POINTER(_I), _P]),

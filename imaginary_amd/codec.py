@@ -118,6 +118,17 @@ def decode(buf: bytes, shrink: int = 1) -> np.ndarray:
     return a[:, :, None] if a.ndim == 2 else np.ascontiguousarray(a)
 
 
+def decode_scale(w: int, h: int, shrink: int) -> int:
+    """The scale decode(buf, shrink) really delivers for a w x h JPEG: Pillow's draft takes the
+    largest of 1, 2, 4, 8 not above min(w // ceil(w / shrink), h // ceil(h / shrink)), so a
+    53-wide file asked for 1/2 decodes at full size.  The decode is ceil(w / scale) x
+    ceil(h / scale)."""
+    if shrink <= 1:
+        return 1
+    fit = min(w // ((w + shrink - 1) // shrink), h // ((h + shrink - 1) // shrink))
+    return max(s for s in (1, 2, 4, 8) if s <= max(fit, 1))
+
+
 YCC_444 = 0   # MIPX_YCC_444: Cb and Cr at full size
 YCC_420 = 1   # MIPX_YCC_420: Cb and Cr at ceil(w / 2) x ceil(h / 2)
 

@@ -214,4 +214,255 @@ int jpegd_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, 
     return launch_check("k_jpegd");
 }
 
+// ---- k_jpegds: the same payload decoded at 1/2, 1/4 or 1/8 (PARITY_ASSUMPTIONS.md row 19) ----
+// libjpeg's shrink-on-load (jdmaster.c, jddctmgr.c, jidctred.c): at scale 1/s every component
+// gets an N x N inverse DCT of its 8 x 8 blocks, which then tile its plane at pitch N.  Y and
+// 4:4:4 chroma take N = 8 / s; 4:2:0 chroma takes N = 16 / s, so all three planes come out at
+// ceil(W / s) x ceil(H / s) and there is no upsampling: the output is three equal planes, the
+// packed MIPX_YCC_444 layout k_ycc.hip takes.  Dequantisation, pass order, the int16 saturation
+// after pass 1 and the final clamp are k_jpegd's; with DS(v, S) = (v + (1 << (S - 1))) >> S:
+//   N = 8: the pass above, S = 11 then 18
+//   N = 4: on i0 i1 i2 i3 i5 i6 i7 (i4 is never read), S = 12 then 19:
+//     t0 = i0 << 14;  t2 = i2 * 15137 - i6 * 6270;  t10 = t0 + t2;  t12 = t0 - t2
+//     a0 = -i7 * 1730 + i5 * 11893 - i3 * 17799 + i1 * 8697
+//     a2 = -i7 * 4176 - i5 * 4926 + i3 * 7373 + i1 * 20995
+//     out = DS(t10 + a2), DS(t12 + a0), DS(t12 - a0), DS(t10 - a2)
+//   N = 2: on i0 i1 i3 i5 i7, S = 13 then 20:
+//     t10 = i0 << 15;  t0 = -i7 * 5906 + i5 * 6967 - i3 * 10426 + i1 * 29692
+//     out = DS(t10 + t0), DS(t10 - t0)
+//   N = 1: DS(d00, 3)
+// Bit-exact against tests/jpegds_ref.py.  Every multiplier is below 2^15 and every operand an
+// int16, so the 24-bit multiplies stay exact modulo 2^32.
+//
+// One launch; a workgroup is uniform in its component and so in its N.  For N = 8, 4, 2 it takes
+// a run of 256 / N consecutive blocks of one block row (32, 64, 128: 4, 8, 16 KiB of contiguous
+// coefficients) and runs k_jpegd's three phases on them.  The run grows as N shrinks because a
+// block gives only N bytes of a plane row: with 256 / N blocks a plane row of the run is 256
+// contiguous bytes at every N.  In phase C a lane holds 8 or 4 bytes of one output row (one block
+// at N = 8 and 4, two neighbouring blocks at N = 2, where half the lanes then rest: the pass is
+// 4 multiplies and a 2-byte store per lane would halve what a store instruction moves), lanes
+// along the run first, so 32 or 64 consecutive lanes store those 256 bytes with dwordx2 or dword
+// stores: at N = 4 and 2 one wave stores one whole row of the run.  Phase A keeps one 16-byte coefficient row per lane and
+// instruction (a wave loads 1 KiB), 8 / N rows per lane, and leaves out the rows no pass reads
+// (row 4 at N = 4; rows 2, 4, 6 at N = 2): their lanes load and write nothing.  Phase B leaves
+// out the same columns.  The LDS image keeps k_jpegd's 144-byte block pitch, so the bank
+// arithmetic is unchanged.  N = 1 occurs only where the plane is the block grid itself
+// (pw = wb, ph = hb), so it is linear: a lane reads the DC terms of 4 consecutive blocks (2 bytes
+// each, 128 apart; nothing else of the block is touched) and stores 4 bytes, a wave 256.
+// Only the last block column of a plane stores fewer than N bytes, and rows past the plane's
+// height are not stored.
+namespace {
+
+struct JpegdsArgs {
+    const u8 *in;
+    u8 *out;
+    long long in_img, out_img;  // bytes per image
+    uint32_t pw, ph;            // size of every plane: ceil(W / s) x ceil(H / s)
+    // [0]: Y, [1]: Cb and Cr
+    uint32_t nidct[2];          // 8, 4, 2 or 1
+    uint32_t wb[2], hb[2];      // real blocks across and down (the file's)
+    uint32_t runs[2];           // runs of 256 / N blocks in one block row (N > 1)
+    uint32_t groups[2];         // workgroups of one image's Y, and of one chroma component
+    uint32_t coef_off[3];       // byte offset of each component's coefficients in an image's input
+};
+
+constexpr int kMaxRun = 128;     // N = 2
+constexpr int kDcPerLane = 4;    // N = 1: blocks of one lane
+
+template <int N>
+__device__ __forceinline__ constexpr bool idct_reads(uint32_t k) {
+    return N == 8 || (N == 4 && k != 4u) || (N == 2 && (k == 0u || (k & 1u)));
+}
+
+// One pass of jidctred.c's 4 x 4 inverse DCT: i[0..3] from i[0 1 2 3 5 6 7]; the rounding
+// constant rides in t0
+template <int S>
+__device__ __forceinline__ void idct4(int i[8]) {
+    const uint32_t t0 = (static_cast<uint32_t>(i[0]) << 14) + (1u << (S - 1));
+    const uint32_t t2 = mad24(i[6], -6270, mul24(i[2], 15137));
+    const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+    const uint32_t a0 = mad24(i[1], 8697, mad24(i[3], -17799, mad24(i[5], 11893, mul24(i[7], -1730))));
+    const uint32_t a2 = mad24(i[1], 20995, mad24(i[3], 7373, mad24(i[5], -4926, mul24(i[7], -4176))));
+    i[0] = descale(t10 + a2, S), i[3] = descale(t10 - a2, S);
+    i[1] = descale(t12 + a0, S), i[2] = descale(t12 - a0, S);
+}
+
+// ... and of its 2 x 2 one: i[0..1] from i[0 1 3 5 7]
+template <int S>
+__device__ __forceinline__ void idct2(int i[8]) {
+    const uint32_t t10 = (static_cast<uint32_t>(i[0]) << 15) + (1u << (S - 1));
+    const uint32_t t0 = mad24(i[1], 29692, mad24(i[3], -10426, mad24(i[5], 6967, mul24(i[7], -5906))));
+    i[0] = descale(t10 + t0, S), i[1] = descale(t10 - t0, S);
+}
+
+template <int N, int PASS>
+__device__ __forceinline__ void idctn(int i[8]) {
+    if constexpr (N == 8) idct8<PASS == 1 ? 11 : 18>(i);
+    if constexpr (N == 4) idct4<PASS == 1 ? 12 : 19>(i);
+    if constexpr (N == 2) idct2<PASS == 1 ? 13 : 20>(i);
+}
+
+// A run of 256 / N blocks of block row `by`, from block bx0, of a component whose coefficients
+// start at `coefs` and whose table is `qt`; `plane` is its output plane
+template <int N>
+__device__ __forceinline__ void jpegds_run(int16_t *blocks, const u8 *coefs, const u8 *qt, u8 *plane, uint32_t by,
+                                           uint32_t bx0, uint32_t wb, uint32_t pw, uint32_t ph) {
+    constexpr uint32_t kR = 256 / N;  // blocks of the run
+    const uint32_t tid = threadIdx.x;
+    const uint32_t sub = tid & 7u;    // the coefficient row (A) or the block column (B) of this lane
+
+    // ---- A: 8 / N coefficient rows per lane, dequantised into LDS; unread rows are left out
+    if (idct_reads<N>(sub)) {
+        uint4 q;
+        __builtin_memcpy(&q, qt + sub * 16u, 16);
+        const u8 *src = coefs + (by * wb + bx0) * 128u;
+#pragma unroll
+        for (uint32_t k = 0; k < 8u / N; ++k) {
+            const uint32_t slot = tid + 256u * k, b = slot >> 3;
+            if (bx0 + b < wb) {
+                uint4 v;
+                __builtin_memcpy(&v, src + slot * 16u, 16);  // any alignment: one global_load_dwordx4
+                *reinterpret_cast<uint4 *>(blocks + b * kBlockPitch + sub * 8u) =
+                    make_uint4(dequant2(v.x, q.x), dequant2(v.y, q.y), dequant2(v.z, q.z), dequant2(v.w, q.w));
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- B: pass 1, 8 / N block columns per lane, in place: N results from the rows that are read
+    if (idct_reads<N>(sub)) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8u / N; ++k) {
+            const uint32_t b = (tid + 256u * k) >> 3;
+            if (bx0 + b < wb) {
+                int16_t *p = blocks + b * kBlockPitch + sub;
+                int d[8];
+#pragma unroll
+                for (int r = 0; r < 8; ++r) d[r] = idct_reads<N>(r) ? p[8 * r] : 0;
+                idctn<N, 1>(d);
+#pragma unroll
+                for (int r = 0; r < N; ++r) p[8 * r] = static_cast<int16_t>(clampi(d[r], -32768, 32767));
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- C: pass 2, 4 or 8 bytes of one output row per lane: one block, two at N = 2 (then half the
+    // lanes rest); kR / kPer consecutive lanes make the 256 bytes of a plane row of the run
+    {
+        constexpr uint32_t kPer = N == 2 ? 2u : 1u;   // blocks of a lane
+        constexpr uint32_t kBytes = kPer * N;         // ... and their bytes of the row
+        const uint32_t b = (tid % (kR / kPer)) * kPer, r = tid / (kR / kPer);
+        const uint32_t x = (bx0 + b) * N, y = by * N + r;
+        if (r < static_cast<uint32_t>(N) && bx0 + b < wb && x < pw && y < ph) {
+            uint32_t o[2] = {0u, 0u};
+#pragma unroll
+            for (uint32_t j = 0; j < kPer; ++j) {
+                if (bx0 + b + j < wb) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(blocks + (b + j) * kBlockPitch + r * 8u);
+                    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+                    int d[8];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        d[2 * k] = static_cast<int>(u[k] << 16) >> 16;
+                        d[2 * k + 1] = static_cast<int>(u[k]) >> 16;
+                    }
+                    idctn<N, 2>(d);
+#pragma unroll
+                    for (int k = 0; k < N; ++k) o[(j * N + k) >> 2] |= sample(d[k]) << (8u * ((j * N + k) & 3u));
+                }
+            }
+            u8 *dst = plane + y * pw + x;
+            if (x + kBytes <= pw) {  // wb * N >= pw: the blocks of these samples are all there
+                __builtin_memcpy(dst, o, kBytes);  // any alignment: one global_store_dwordx2 / dword
+            } else {  // the end of the plane row: pw - x of the samples are real
+                for (uint32_t k = 0; x + k < pw; ++k) dst[k] = static_cast<u8>(o[k >> 2] >> (8u * (k & 3u)));
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_jpegds(const JpegdsArgs a) {
+    __shared__ __attribute__((aligned(16))) int16_t blocks[kMaxRun * kBlockPitch];
+    const u8 *in = a.in + blockIdx.y * a.in_img;
+    u8 *out = a.out + blockIdx.y * a.out_img;
+    // which component and group: uniform over the workgroup
+    uint32_t g = blockIdx.x, comp = 0;
+    if (g >= a.groups[0]) {
+        g -= a.groups[0];
+        comp = 1;
+        if (g >= a.groups[1]) g -= a.groups[1], comp = 2;
+    }
+    const uint32_t c = comp ? 1u : 0u;
+    const uint32_t n = a.nidct[c], wb = a.wb[c], pw = a.pw, ph = a.ph;
+    const u8 *coefs = in + MIPX_JPEGD_HEADER_BYTES + a.coef_off[comp];
+    const u8 *qt = in + comp * 128u;
+    u8 *plane = out + comp * (pw * ph);
+    if (n == 1u) {  // the plane is the block grid: sample i is the DC term of block i
+        const uint32_t total = wb * a.hb[c];
+        const uint32_t i0 = (g * 256u + threadIdx.x) * kDcPerLane;
+        if (i0 >= total) return;
+        unsigned short q0;
+        __builtin_memcpy(&q0, qt, 2);
+        uint32_t o = 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < static_cast<uint32_t>(kDcPerLane); ++k) {
+            if (i0 + k < total) {
+                unsigned short v;
+                __builtin_memcpy(&v, coefs + (i0 + k) * 128u, 2);  // any alignment: one global_load_ushort
+                const int d = static_cast<int16_t>(static_cast<unsigned short>(static_cast<uint32_t>(v) * q0));
+                o |= sample((d + 4) >> 3) << (8u * k);
+            }
+        }
+        if (i0 + kDcPerLane <= total) {
+            __builtin_memcpy(plane + i0, &o, 4);  // any alignment: one global_store_dword
+        } else {
+            for (uint32_t k = 0; i0 + k < total; ++k) plane[i0 + k] = static_cast<u8>(o >> (8u * k));
+        }
+        return;
+    }
+    const uint32_t by = g / a.runs[c], bx0 = (g - by * a.runs[c]) * (256u / n);
+    if (n == 8u) jpegds_run<8>(blocks, coefs, qt, plane, by, bx0, wb, pw, ph);
+    else if (n == 4u) jpegds_run<4>(blocks, coefs, qt, plane, by, bx0, wb, pw, ph);
+    else jpegds_run<2>(blocks, coefs, qt, plane, by, bx0, wb, pw, ph);
+}
+
+}  // namespace
+
+// w x h is the file's size.  The caller has checked that the payload and the RGB at the output
+// size are below 2^32 bytes, and that shrink is 2, 4 or 8.
+int jpegds_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, int shrink, hipStream_t st) {
+    const bool sub = layout == MIPX_YCC_420;
+    const uint32_t s = static_cast<uint32_t>(shrink);
+    JpegdsArgs a;
+    a.in = d_in, a.out = d_planes;
+    a.in_img = static_cast<long long>(mipx_jpegd_bytes(w, h, layout));
+    a.pw = (static_cast<uint32_t>(w) + s - 1u) / s, a.ph = (static_cast<uint32_t>(h) + s - 1u) / s;
+    a.out_img = 3ll * a.pw * a.ph;
+    const uint32_t cw[2] = {static_cast<uint32_t>(w), sub ? (static_cast<uint32_t>(w) + 1u) / 2u : w};
+    const uint32_t ch[2] = {static_cast<uint32_t>(h), sub ? (static_cast<uint32_t>(h) + 1u) / 2u : h};
+    a.nidct[0] = 8u / s, a.nidct[1] = sub ? 16u / s : 8u / s;
+    long long total = 0;
+    for (int c = 0; c < 2; ++c) {
+        a.wb[c] = (cw[c] + 7u) / 8u, a.hb[c] = (ch[c] + 7u) / 8u;
+        if (a.nidct[c] == 1u) {  // linear over the block grid, which is the plane
+            if (a.wb[c] != a.pw || a.hb[c] != a.ph) return MIPX_EINVAL;
+            const uint32_t per = 256u * kDcPerLane;
+            a.runs[c] = 1u;
+            a.groups[c] = static_cast<uint32_t>((static_cast<unsigned long long>(a.wb[c]) * a.hb[c] + per - 1u) / per);
+        } else {
+            const uint32_t run = 256u / a.nidct[c];
+            a.runs[c] = (a.wb[c] + run - 1u) / run;
+            a.groups[c] = a.runs[c] * a.hb[c];
+        }
+        total += static_cast<long long>(a.groups[c]) * (c ? 2 : 1);
+    }
+    if (!grid_ok(total)) return MIPX_EUNSUPPORTED;
+    a.coef_off[0] = 0u;
+    a.coef_off[1] = a.wb[0] * a.hb[0] * 128u;
+    a.coef_off[2] = a.coef_off[1] + a.wb[1] * a.hb[1] * 128u;
+    hipLaunchKernelGGL(k_jpegds, dim3(static_cast<unsigned>(total), n), dim3(256), 0, st, a);
+    return launch_check("k_jpegds");
+}
+
 }  // namespace mipx

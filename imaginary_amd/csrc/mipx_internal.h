@@ -204,6 +204,9 @@ int ycc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout,
 int jpegc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, int quality, hipStream_t st);
 // k_jpegd.hip: quantisation tables + quantised coefficients (MIPX_OP_JPEGD) -> the packed planes ycc_launch takes
 int jpegd_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, hipStream_t st);
+// the same payload of a w x h file at 1/shrink (2, 4, 8) -> three planes of ceil(w / shrink) x ceil(h / shrink),
+// packed as MIPX_YCC_444
+int jpegds_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, int shrink, hipStream_t st);
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,
@@ -215,7 +218,7 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
 
 // mipx_planner.cpp: bytes per image of the plan's input buffer: w * h * bands, or the packed
 // planes when step 0 is MIPX_OP_YCC, the coefficient payload when it is MIPX_OP_JPEGD (header
-// fields already validated)
+// fields already validated): of the file's size, which a scaled step carries in a[2], a[3]
 size_t plan_input_bytes(const mipx_plan *p);
 // bytes per image of the plan's output buffer: out_w * out_h * out_bands, or the coefficients
 // when the last step is MIPX_OP_JPEGC (plan already validated)

@@ -176,6 +176,31 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
     return ycc_launch(planes, d_out, n, w, h, layout, as_stream(stream));
 }
 
+int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t file_w, int32_t file_h,
+                                int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes, void *stream) {
+    if (shrink == 1) return mipx_op_jpegd_to_rgb(d_in, d_out, n, file_w, file_h, layout, d_ws, ws_bytes, stream);
+    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
+        (shrink != 2 && shrink != 4 && shrink != 8))
+        return MIPX_EINVAL;
+    const int ow = static_cast<int>((static_cast<long long>(file_w) + shrink - 1) / shrink);
+    const int oh = static_cast<int>((static_cast<long long>(file_h) + shrink - 1) / shrink);
+    // byte offsets inside an image are 32-bit in both kernels
+    if (mipx_jpegd_bytes(file_w, file_h, layout) > 0xffffffffull || 3ull * ow * oh > 0xffffffffull) {
+        set_error("jpeg coefficients to rgb at 1/%d: image %dx%d too large (an image's bytes >= 2^32)", shrink, file_w,
+                  file_h);
+        return MIPX_EUNSUPPORTED;
+    }
+    if (!d_ws || ws_bytes < op_workspace_bytes(MIPX_OP_JPEGD, n, ow, oh, 3, 0, 0)) {
+        set_error("jpeg coefficients to rgb at 1/%d: workspace %zu < %zu bytes", shrink, ws_bytes,
+                  op_workspace_bytes(MIPX_OP_JPEGD, n, ow, oh, 3, 0, 0));
+        return MIPX_EINVAL;
+    }
+    uint8_t *planes = static_cast<uint8_t *>(d_ws);  // three ow x oh planes: no upsampling at these scales
+    const int e = jpegds_launch(d_in, planes, n, file_w, file_h, layout, shrink, as_stream(stream));
+    if (e) return e;
+    return ycc_launch(planes, d_out, n, ow, oh, MIPX_YCC_444, as_stream(stream));
+}
+
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t bands, double xscale,
                    double yscale, int32_t extend, void *stream) {
     if (!d_in || !d_out || !geom_ok(n, w, h, bands) || !(xscale > 0) || !(yscale > 0)) return MIPX_EINVAL;

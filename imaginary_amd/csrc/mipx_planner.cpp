@@ -619,7 +619,11 @@ extern "C" size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout) {
 
 size_t mipx::plan_input_bytes(const mipx_plan *p) {
     if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_YCC) return mipx_ycc_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
-    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_JPEGD) return mipx_jpegd_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
+    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_JPEGD) {
+        const mipx_step &s = p->steps[0];  // decoded at 1/a[1]: the payload is the a[2] x a[3] file's
+        if (s.a[1] > 1) return mipx_jpegd_bytes(s.a[2], s.a[3], s.a[0]);
+        return mipx_jpegd_bytes(p->in_w, p->in_h, s.a[0]);
+    }
     return static_cast<size_t>(p->in_w) * p->in_h * p->in_bands;
 }
 
@@ -703,19 +707,37 @@ extern "C" size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout) {
     return coefs ? MIPX_JPEGD_HEADER_BYTES + coefs : 0;
 }
 
-extern "C" int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout) {
+// shrink 1: the full-size step; 2, 4, 8: the step that decodes the file_w x file_h file at that scale
+static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w, int32_t file_h,
+                           const char *who) {
     if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
     if (plan->in_bands != 3) {
-        mipx::set_error("mipx_plan_set_jpegd_input: the plan takes %d bands, a YCbCr JPEG makes 3", plan->in_bands);
+        mipx::set_error("%s: the plan takes %d bands, a YCbCr JPEG makes 3", who, plan->in_bands);
         return MIPX_EINVAL;
     }
     if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_YCC || plan->steps[0].op == MIPX_OP_JPEGD)) {
-        mipx::set_error("mipx_plan_set_jpegd_input: the plan already takes %s input",
+        mipx::set_error("%s: the plan already takes %s input", who,
                         plan->steps[0].op == MIPX_OP_YCC ? "planar" : "coefficient");
         return MIPX_EINVAL;
     }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
-        mipx::set_error("mipx_plan_set_jpegd_input: the plan is full (MIPX_MAX_STEPS)");
+        mipx::set_error("%s: the plan is full (MIPX_MAX_STEPS)", who);
+        return MIPX_EINVAL;
+    }
+    if (shrink != 1) {
+        if (shrink != 2 && shrink != 4 && shrink != 8) {
+            mipx::set_error("%s: shrink %d is not 1, 2, 4 or 8", who, shrink);
+            return MIPX_EINVAL;
+        }
+        if (file_w <= 0 || file_h <= 0 || (static_cast<long long>(file_w) + shrink - 1) / shrink != plan->in_w ||
+            (static_cast<long long>(file_h) + shrink - 1) / shrink != plan->in_h) {
+            mipx::set_error("%s: a %dx%d file at 1/%d does not give the plan's %dx%d", who, file_w, file_h, shrink,
+                            plan->in_w, plan->in_h);
+            return MIPX_EINVAL;
+        }
+    } else if (file_w != plan->in_w || file_h != plan->in_h) {
+        mipx::set_error("%s: a %dx%d file at full size does not give the plan's %dx%d", who, file_w, file_h, plan->in_w,
+                        plan->in_h);
         return MIPX_EINVAL;
     }
     for (int i = plan->n_steps; i > 0; --i) plan->steps[i] = plan->steps[i - 1];
@@ -724,8 +746,19 @@ extern "C" int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout) {
     std::memset(&s, 0, sizeof(s));
     s.op = MIPX_OP_JPEGD;
     s.a[0] = layout;
+    if (shrink != 1) s.a[1] = shrink, s.a[2] = file_w, s.a[3] = file_h;
     s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = 3;
     return MIPX_OK;
+}
+
+extern "C" int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout) {
+    if (!plan) return MIPX_EINVAL;
+    return set_jpegd_input(plan, layout, 1, plan->in_w, plan->in_h, "mipx_plan_set_jpegd_input");
+}
+
+extern "C" int mipx_plan_set_jpegd_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
+                                                int32_t file_h) {
+    return set_jpegd_input(plan, layout, shrink, file_w, file_h, "mipx_plan_set_jpegd_input_scaled");
 }
 
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {

@@ -17,7 +17,7 @@ __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
            "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420",
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
-           "plan_set_jpegd_input", "jpegd_bytes", "jpegd_to_rgb",
+           "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -290,6 +290,13 @@ def _jpegd_layout(plan: MipxPlan):
     return plan.steps[0].a[0] if plan.n_steps > 0 and plan.steps[0].op == OP_JPEGD else None
 
 
+def _jpegd_file_size(plan: MipxPlan):
+    """(w, h) of the file whose payload a JPEGD plan takes: the plan's input size, or what a
+    scaled step (a[1] = 2, 4, 8) carries in a[2], a[3]."""
+    a = plan.steps[0].a
+    return (a[2], a[3]) if a[1] > 1 else (plan.in_w, plan.in_h)
+
+
 def _packed_input(plan: MipxPlan) -> bool:
     """Whether the plan's input is bytes per image (planes or a coefficient payload), not pixels."""
     return _ycc_layout(plan) is not None or _jpegd_layout(plan) is not None
@@ -301,7 +308,7 @@ def _planes(plan: MipxPlan, planes) -> np.ndarray:
     if x.ndim == 1:
         x = x[None]
     if _jpegd_layout(plan) is not None:
-        need, what = jpegd_bytes(plan.in_w, plan.in_h, _jpegd_layout(plan)), "coefficient"
+        need, what = jpegd_bytes(*_jpegd_file_size(plan), _jpegd_layout(plan)), "coefficient"
     else:
         need, what = ycc_bytes(plan.in_w, plan.in_h, _ycc_layout(plan)), "planar"
     if x.ndim != 2 or x.shape[1] != need:
@@ -320,6 +327,16 @@ def plan_set_jpegd_input(plan: MipxPlan, layout: int) -> MipxPlan:
     takes a JPEG's quantisation tables and quantised coefficients (codec.decode_jpeg_coefs;
     YCC_444 or YCC_420) instead of RGB pixels."""
     check(lib.mipx_plan_set_jpegd_input(C.byref(plan), layout), "mipx_plan_set_jpegd_input")
+    return plan
+
+
+def plan_set_jpegd_input_scaled(plan: MipxPlan, layout: int, shrink: int, file_w: int, file_h: int) -> MipxPlan:
+    """mipx_plan_set_jpegd_input_scaled on `plan` (in place; returned for convenience): the plan,
+    made for the ceil(file_w / shrink) x ceil(file_h / shrink) decode, then takes the full-size
+    file's coefficient payload and decodes it at 1/shrink (1, 2, 4, 8) as libjpeg's
+    shrink-on-load does.  shrink 1 is plan_set_jpegd_input."""
+    check(lib.mipx_plan_set_jpegd_input_scaled(C.byref(plan), layout, shrink, file_w, file_h),
+          "mipx_plan_set_jpegd_input_scaled")
     return plan
 
 
@@ -614,6 +631,29 @@ def jpegd_to_rgb(payload: np.ndarray, w: int, h: int, layout: int) -> np.ndarray
     return dout.download((n, h, w, 3))
 
 
+def jpegd_to_rgb_scaled(payload: np.ndarray, w: int, h: int, layout: int, shrink: int) -> np.ndarray:
+    """mipx_op_jpegd_to_rgb_scaled on the coefficient payloads of w x h files, (bytes,) or
+    (n, bytes) uint8; returns (n, ceil(h / shrink), ceil(w / shrink), 3)."""
+    sync_tuning()
+    x = np.ascontiguousarray(payload, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x[None]
+    need = jpegd_bytes(w, h, layout)
+    if x.ndim != 2 or need == 0 or x.shape[1] != need or shrink not in (1, 2, 4, 8):
+        raise ValueError(f"payload of shape {np.shape(payload)} for {w}x{h} layout {layout} at 1/{shrink}: "
+                         f"{need} bytes per image, shrink 1, 2, 4 or 8")
+    n, ow, oh = x.shape[0], -(-w // shrink), -(-h // shrink)
+    what = "mipx_op_jpegd_to_rgb_scaled"
+    din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
+    dout = _dev("out", what, n * oh * ow * 3, ow * 3)
+    wsb = lib.mipx_op_workspace_bytes(OP_JPEGD, n, ow, oh, 3, 0.0, 0.0)
+    ws = _dev("ws", what, wsb)
+    check(lib.mipx_op_jpegd_to_rgb_scaled(din.ptr, dout.ptr, n, w, h, layout, shrink, ws.ptr, wsb, None), what)
+    synchronize()
+    _check_guards(what, din, dout, ws)
+    return dout.download((n, oh, ow, 3))
+
+
 def smartcrop_origins(imgs: np.ndarray, cw: int, ch: int) -> np.ndarray:
     sync_tuning()
     x = _batch(imgs)
@@ -633,7 +673,7 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
             junk: Optional[int] = None) -> np.ndarray:
     """mipx_execute_dev on a batch of host images (uploads, runs the plan, downloads); for a
     plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes),
-    and for one that takes coefficient input (plan_set_jpegd_input), on payloads of the same shapes;
+    and for one that takes coefficient input (plan_set_jpegd_input[_scaled]), on payloads of the same shapes;
     a plan that gives coefficients (plan_set_jpegc_output) returns (n, jpegc_bytes / 2) int16.
     junk: fill the workspace (the ping-pong intermediates) and the output with this byte
     first, so a step that reads outside what the steps before it wrote shows up."""

@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _abi, codec
 from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_textmark, plan_chain, plan_make,
-                     plan_set_jpegc_output, plan_set_jpegd_input, plan_set_ycc_input, plan_textmark_geometry)
+                     plan_set_jpegc_output, plan_set_jpegd_input, plan_set_jpegd_input_scaled, plan_set_ycc_input, plan_textmark_geometry)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -492,7 +492,7 @@ class JpegCoefs:
 
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
             text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None,
-            jpeg_dct: Optional[tuple] = None):
+            jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -508,7 +508,10 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     shape: the plan takes the JPEG's packed planes and the engine upsamples and converts.
     With `jpeg_dct` = (payload, layout) (codec.decode_jpeg_coefs) likewise: the plan takes the
     file's quantisation tables and coefficients and the engine runs the inverse DCT too; it
-    takes precedence over `ycc`.
+    takes precedence over `ycc`.  With `jpeg_dct_shrink` too, a plan that asks for load_shrink > 1
+    also takes them: the engine decodes the full-size file's payload at the scale the host codec
+    would deliver (codec.decode_scale), as libjpeg's shrink-on-load does, and `redecode` is not
+    called.
     With `jpeg_quality` (1..100) and a 3-band result, the plan ends with the coefficient step
     (4:2:0 below Q 90, 4:4:4 from Q 90, as codec.encode samples) and a JpegCoefs is returned;
     results of other band counts come back as pixels."""
@@ -523,7 +526,12 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
         inp.wm_w, inp.wm_h, inp.wm_bands = wm.shape[1], wm.shape[0], wm.shape[2]
     try:
         plan = plan_make(make_opts(**opts), inp)
-        if plan.load_shrink > 1:
+        dct_scale = None   # the scale the engine decodes the coefficients at, when it shrinks on load
+        if plan.load_shrink > 1 and jpeg_dct is not None and jpeg_dct_shrink and chain is None:
+            dct_scale = codec.decode_scale(img.w, img.h, plan.load_shrink)
+            inp.decoded_w, inp.decoded_h = -(-img.w // dct_scale), -(-img.h // dct_scale)
+            plan = plan_make(make_opts(**opts), inp)
+        elif plan.load_shrink > 1:
             if redecode is None:
                 raise ImaginaryError("shrink-on-load requested but no host decoder given", 500)
             px = redecode(img, plan.load_shrink)
@@ -533,7 +541,10 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
             raise ImaginaryError("decoded size does not match the header", 500)
         if text is not None:
             wm = _add_textmark(plan, text)
-        if jpeg_dct is not None:
+        if jpeg_dct is not None and dct_scale is not None:
+            plan_set_jpegd_input_scaled(plan, jpeg_dct[1], dct_scale, img.w, img.h)
+            px = jpeg_dct[0]
+        elif jpeg_dct is not None:
             if plan.load_shrink > 1 or chain is not None:
                 raise ImaginaryError("coefficient input needs the full-size decode of a single request", 500)
             plan_set_jpegd_input(plan, jpeg_dct[1])
@@ -558,7 +569,8 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 
 
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
-                  ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False) -> Image:
+                  ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
+                  jpeg_dct_shrink: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -572,7 +584,10 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     quantised coefficients (codec.decode_jpeg_coefs), so the host only entropy-decodes, when the
     request decodes at full size; the bytes are the same either way.  Shrink-on-load requests, the
     rotate-and-re-encode path and every file that decoder declines keep today's path, which is
-    `ycc`'s when that is set too: of the two, jpeg_dct is tried first."""
+    `ycc`'s when that is set too: of the two, jpeg_dct is tried first.
+    jpeg_dct_shrink: with jpeg_dct, a shrink-on-load request that does not rotate goes to the engine as
+    coefficients too, decoded there at the scale codec.decode(buf, shrink) would deliver; the bytes
+    are the same either way."""
     opts = dict(opts)
     out_type = str(opts.pop("type", "") or "")
     quality = int(opts.pop("quality", 0) or 0)
@@ -606,8 +621,11 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     if plan.load_shrink > 1 and itype == "jpeg" and rotates and not opts.get("no_auto_rotate"):
         px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text)
     elif plan.load_shrink > 1:  # process() re-plans on the codec-shrunk size
+        take = jpeg_dct and jpeg_dct_shrink and hdr.bands == 3 and itype == "jpeg" and not rotates
+        dct = codec.decode_jpeg_coefs(buf) if take else None
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
-        px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq)
+        px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
+                     jpeg_dct_shrink=dct is not None)
     else:
         dct = codec.decode_jpeg_coefs(buf) if jpeg_dct and hdr.bands == 3 and itype == "jpeg" else None
         planes = codec.decode_ycc(buf) if dct is None and ycc and hdr.bands == 3 else None

@@ -144,7 +144,12 @@ enum {
     MIPX_OP_JPEGD        /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, never together
                             with MIPX_OP_YCC; the input buffer is then the file's quantisation tables and
                             quantised coefficients (mipx_plan_set_jpegd_input)
-                                  (libjpeg dequantisation, inverse DCT, upsample, colour conversion) */
+                                  (libjpeg dequantisation, inverse DCT, upsample, colour conversion)
+                            a[1] = shrink: 0 or 1 decode at full size; 2, 4, 8 decode at that fraction
+                            (libjpeg's shrink-on-load), and then a[2], a[3] = the file's width and height,
+                            the payload is that file's, and the plan's in_w x in_h must be
+                            ceil(a[2] / a[1]) x ceil(a[3] / a[1]) (mipx_plan_set_jpegd_input_scaled);
+                            any other a[1] is MIPX_EINVAL */
 };
 
 /* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
@@ -181,7 +186,14 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * and converts as MIPX_OP_YCC does.  The result is libjpeg-turbo's for every file an encoder
  * writes; where a sum saturates or wraps (corrupt or hand-made coefficients) it is the rule's,
  * which tests/jpegd_ref.py restates, not the library's (PARITY_ASSUMPTIONS.md row 18).  Images
- * and both pointers start on any byte. */
+ * and both pointers start on any byte.
+ *    The same payload decodes at 1/2, 1/4 and 1/8 as libjpeg's scaled decode does (jdmaster.c,
+ * jidctred.c; what jpeg_read_coefficients gives does not depend on the scale).  The output is
+ * ceil(w / s) x ceil(h / s).  Y and 4:4:4 chroma blocks get the 4 x 4, 2 x 2 or 1 x 1 inverse
+ * DCT; 4:2:0 chroma blocks get the next larger one (8 x 8, 4 x 4, 2 x 2), so chroma comes out at
+ * the output size and nothing is upsampled; the conversion is the 4:4:4 one.  Bit for bit
+ * libjpeg-turbo's on files an encoder writes, tests/jpegds_ref.py's rule elsewhere
+ * (PARITY_ASSUMPTIONS.md row 19). */
 #define MIPX_JPEGD_HEADER_BYTES 384
 
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
@@ -292,7 +304,8 @@ int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
  * other steps move up).  The plan's geometry is unchanged; what changes is the input buffer,
  * which is then mipx_jpegd_bytes(in_w, in_h, layout) bytes per image for mipx_execute_dev, and
  * for mipx_submit a mipx_img of w = in_w, h = in_h, bands = 3, stride = 0 whose data is the
- * payload (anything else is MIPX_EINVAL).  Use it on plans with load_shrink 1.  In a
+ * payload (anything else is MIPX_EINVAL).  Use it on plans with load_shrink 1
+ * (mipx_plan_set_jpegd_input_scaled serves the others).  In a
  * mipx_plan_chain the step may appear in stage 0 only.  It composes with
  * mipx_plan_add_textmark and mipx_plan_set_jpegc_output in either call order.  MIPX_EINVAL,
  * with the plan untouched, for an unknown layout, in_bands != 3, a plan that already starts
@@ -300,6 +313,17 @@ int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
  * a plan that starts with this step). */
 size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout);
 int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout);
+/* mipx_plan_set_jpegd_input for a file decoded at 1/shrink (libjpeg's shrink-on-load; works
+ * without a GPU).  Plan as usual on the decoded size, in_w x in_h = ceil(file_w / shrink) x
+ * ceil(file_h / shrink), then call this: the step at index 0 carries shrink and the file's size,
+ * and the input buffer is the unchanged payload of the full-size file,
+ * mipx_jpegd_bytes(file_w, file_h, layout) bytes per image (for mipx_submit a mipx_img of
+ * w = in_w, h = in_h, bands = 3, stride = 0 with that payload as data).  shrink 1 gives exactly
+ * the plan mipx_plan_set_jpegd_input gives.  Same composition rules and refusals as
+ * mipx_plan_set_jpegd_input; also MIPX_EINVAL, with the plan untouched, for a shrink other than
+ * 1, 2, 4, 8 and for a file size that does not give in_w x in_h at that shrink. */
+int mipx_plan_set_jpegd_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
+                                     int32_t file_h);
 /* imaginary image.go:190 calculateDestinationFitDimension */
 int mipx_fit_dimension(int32_t image_w, int32_t image_h, int32_t fit_w, int32_t fit_h,
                        int32_t *out_w, int32_t *out_h);
@@ -388,6 +412,15 @@ int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
  * or RGB is 2^32 bytes or more (the kernels' byte offsets inside an image are 32-bit). */
 int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                          int32_t layout, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same n payloads of file_w x file_h files decoded at 1/shrink -> n x oh x ow x 3 RGB with
+ * ow = ceil(file_w / shrink), oh = ceil(file_h / shrink); shrink 1 forwards to
+ * mipx_op_jpegd_to_rgb.  The workspace takes three ow x oh planes:
+ * mipx_op_workspace_bytes(MIPX_OP_JPEGD, n, ow, oh, 3, 0, 0) bytes.  MIPX_EINVAL and
+ * MIPX_EUNSUPPORTED as for mipx_op_jpegd_to_rgb (the RGB bound is on the output size), and
+ * MIPX_EINVAL for a shrink other than 1, 2, 4, 8. */
+int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t file_w, int32_t file_h,
+                                int32_t layout, int32_t shrink, void *d_workspace, size_t workspace_bytes,
+                                void *stream);
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                    int32_t bands, double xscale, double yscale, int32_t extend, void *stream);
 int mipx_op_zoom(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,

@@ -7,8 +7,9 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py ycc420 --w 3840 --h 2160 --n 64
     python scripts/op_bench.py jpegc420 --w 3840 --h 2160 --n 64 --q 75
     python scripts/op_bench.py jpegd420 --w 3840 --h 2160 --n 64 --q 75
+    python scripts/op_bench.py jpegds420 --w 3840 --h 2160 --n 64 --q 75 --shrink 4
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
-         jpegc420 jpegc444 jpegd420 jpegd444
+         jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444
 """
 import argparse
 import ctypes as C
@@ -44,7 +45,9 @@ def main():
     ap.add_argument("--mh", type=int, default=0, help="textmark / watermark: mask or watermark height (0 = mw / 5)")
     ap.add_argument("--margin", type=int, default=-1, help="textmark: margin (-1 = the mask width, bimg's default)")
     ap.add_argument("--opacity", type=float, default=0.25)
-    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444 / jpegd420 / jpegd444: JPEG quality")
+    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444 / jpegd* : JPEG quality")
+    ap.add_argument("--shrink", type=int, default=2, choices=[1, 2, 4, 8],
+                    help="jpegds420 / jpegds444: decode the w x h file's coefficients at 1/shrink")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -95,16 +98,20 @@ def main():
         b = ob = 3              # "out" names the image the step consumes; its bytes are out_img
         layout = 1 if a.op == "jpegc420" else 0
         in_img, out_img = w * h * 3, lib.mipx_jpegc_bytes(w, h, layout)
-    if a.op in ("jpegd420", "jpegd444"):   # quantisation tables + quantised DCT coefficients in, RGB out
+    JPEGD = ("jpegd420", "jpegd444", "jpegds420", "jpegds444")
+    if a.op in JPEGD:   # quantisation tables + quantised DCT coefficients in, RGB out
         b = ob = 3
-        layout = 1 if a.op == "jpegd420" else 0
+        layout = 1 if a.op.endswith("420") else 0
         in_img = lib.mipx_jpegd_bytes(w, h, layout)
+        if a.op.startswith("jpegds"):   # ... at 1/shrink: the same payload, RGB at the decoded size
+            ow, oh = -(-w // a.shrink), -(-h // a.shrink)
+            out_img = ow * oh * 3
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
     y = torch.empty((n * out_img,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
-    if a.op in ("jpegd420", "jpegd444"):
+    if a.op in JPEGD:
         # what a decoder hands over: the coefficients the engine's own encoder makes of random pixels
         # at --q (zero runs and small values, not noise), behind that quality's tables
         import numpy as np
@@ -160,6 +167,8 @@ def main():
             return lib.mipx_op_rgb_to_jpegc(X, Y, n, w, h, layout, a.q, sp)
         if a.op in ("jpegd420", "jpegd444"):
             return lib.mipx_op_jpegd_to_rgb(X, Y, n, w, h, layout, WS, WSB, sp)
+        if a.op in ("jpegds420", "jpegds444"):
+            return lib.mipx_op_jpegd_to_rgb_scaled(X, Y, n, w, h, layout, a.shrink, WS, WSB, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -190,6 +199,8 @@ def main():
     alg = n * (in_img + out_img)   # bytes = input + output
     line = {"op": a.op, "w": w, "h": h, "b": b, "n": n, "s": a.s, "s2": s2, "out": [ow, oh, ob],
             "sampling": ["corner", "centre"][lib.mipx_reduce_sampling()]}
+    if a.op.startswith("jpegds"):
+        line["shrink"] = a.shrink
     if not a.ab:
         ms = measure()
         print(json.dumps({**line, "ms": round(ms, 4), "alg_GBps": round(alg / ms / 1e6, 1)}))
