@@ -30,12 +30,12 @@ TYPES = {"unknown": 0, "jpeg": 1, "webp": 2, "png": 3, "tiff": 4, "gif": 5, "pdf
          "magick": 8, "heif": 9, "avif": 10}
 
 (OP_ROT, OP_FLIP, OP_SHRINK, OP_REDUCE, OP_EXTRACT, OP_EMBED, OP_SMARTCROP, OP_BLUR, OP_WATERMARK,
- OP_AFFINE, OP_ZOOM, OP_FLATTEN, OP_BW, OP_TEXTMARK, OP_YCC, OP_JPEGC, OP_JPEGD) = range(1, 18)
+ OP_AFFINE, OP_ZOOM, OP_FLATTEN, OP_BW, OP_TEXTMARK, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT) = range(1, 19)
 OP_NAMES = {OP_ROT: "rot", OP_FLIP: "flip", OP_SHRINK: "shrink", OP_REDUCE: "reduce",
             OP_EXTRACT: "extract", OP_EMBED: "embed", OP_SMARTCROP: "smartcrop",
             OP_BLUR: "blur", OP_WATERMARK: "watermark", OP_AFFINE: "affine", OP_ZOOM: "zoom",
             OP_FLATTEN: "flatten", OP_BW: "bw", OP_TEXTMARK: "textmark", OP_YCC: "ycc", OP_JPEGC: "jpegc",
-            OP_JPEGD: "jpegd"}
+            OP_JPEGD: "jpegd", OP_JPEGRT: "jpegrt"}
 YCC_444 = 0   # planar JPEG input, coefficient input and output (MIPX_YCC_*): Cb, Cr at full size ...
 YCC_420 = 1   # ... or at ceil(w / 2) x ceil(h / 2)
 INTERPRETATION_SRGB = 22
@@ -140,6 +140,7 @@ _SIG = {
     "mipx_jpegd_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegd_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
     "mipx_plan_set_jpegd_input_scaled": (C.c_int, [C.POINTER(MipxPlan), _I, _I, _I, _I]),
+    "mipx_plan_add_jpeg_roundtrip": (C.c_int, [C.POINTER(MipxPlan), _I, _I, _I]),
     "mipx_submit": (C.c_int, [C.c_int, C.POINTER(MipxPlan), C.POINTER(MipxImg), C.POINTER(MipxImg),
                               C.POINTER(MipxImg), C.POINTER(C.c_uint64)]),
     "mipx_wait": (C.c_int, [C.c_uint64, C.c_int]),
@@ -162,6 +163,7 @@ _SIG = {
     "mipx_op_rgb_to_jpegc": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P]),
     "mipx_op_jpegd_to_rgb": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_jpegd_to_rgb_scaled": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "mipx_op_jpeg_roundtrip": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_affine": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P]),
     "mipx_op_zoom": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _I, _P]),
     "mipx_op_flatten": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, C.POINTER(_I), _P]),

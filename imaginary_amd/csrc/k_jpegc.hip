@@ -29,11 +29,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "jpeg_dct.h"
 
 namespace mipx {
 namespace {
 
 using namespace dev;
+using namespace jfdct;
 
 struct JpegcArgs {
     const u8 *in;
@@ -47,93 +49,7 @@ struct JpegcArgs {
     uint32_t gx;                // strips across one image
 };
 
-constexpr int kBlocks = 48;      // blocks of one strip
-constexpr int kBlockPitch = 72;  // int16s between blocks in LDS: 64 + 8, so 8 blocks' columns cover 32 banks
 constexpr uint32_t kNoBlock = 0xffffffffu;
-
-// a * k + c with 24-bit signed a and k: the full-rate v_mad_i32_i24 (k_ycc.hip)
-__device__ __forceinline__ int mad24(int a, int k, int c) {
-    int r;
-    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(k), "v"(c));
-    return r;
-}
-__device__ __forceinline__ int mul24(int a, int k) {
-    int r;
-    asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "s"(k), "v"(a));
-    return r;
-}
-
-// 4 pixels of one row from column x0: bytes 3 k + c of d; past w - 1 the last pixel repeats
-__device__ __forceinline__ void load_rgb4(const u8 *row, uint32_t x0, uint32_t w, uint32_t d[3]) {
-    if (x0 + 4u <= w) {
-        __builtin_memcpy(d, row + 3u * x0, 12);  // any alignment: one global_load_dwordx3
-        return;
-    }
-    d[0] = d[1] = d[2] = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const u8 *p = row + 3u * min(x0 + k, w - 1u);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[(3 * k + c) >> 2] |= static_cast<uint32_t>(p[c]) << (8 * ((3 * k + c) & 3));
-    }
-}
-__device__ __forceinline__ int rgb_byte(const uint32_t d[3], int i) {
-    return static_cast<int>((d[i >> 2] >> (8 * (i & 3))) & 255u);
-}
-// jccolor.c on the 4 pixels of d
-__device__ __forceinline__ void rgb_ycc4(const uint32_t d[3], int y[4], int cb[4], int cr[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int r = rgb_byte(d, 3 * k), g = rgb_byte(d, 3 * k + 1), b = rgb_byte(d, 3 * k + 2);
-        y[k] = mad24(r, 19595, mad24(g, 38470, mad24(b, 7471, 32768))) >> 16;
-        cb[k] = mad24(r, -11059, mad24(g, -21709, mad24(b, 32768, 8388608 + 32767))) >> 16;
-        cr[k] = mad24(r, 32768, mad24(g, -27439, mad24(b, -5329, 8388608 + 32767))) >> 16;
-    }
-}
-__device__ __forceinline__ uint32_t pack16(int lo, int hi) {
-    return (static_cast<uint32_t>(lo) & 0xffffu) | (static_cast<uint32_t>(hi) << 16);
-}
-// 4 samples - 128 as int16 at s (8-byte aligned)
-__device__ __forceinline__ void put4(int16_t *s, const int v[4]) {
-    *reinterpret_cast<uint2 *>(s) = make_uint2(pack16(v[0] - 128, v[1] - 128), pack16(v[2] - 128, v[3] - 128));
-}
-
-// One 8-point pass of jfdctint.c in place.  FIRST: the rows pass (outputs scaled up by
-// PASS1_BITS = 2); otherwise the columns pass.  |d| <= 128 before the first pass and <= 3784
-// before the second, so every product has 24-bit operands and every sum fits int32; the
-// rounding constant of the descale rides in the first term of each sum.
-template <bool FIRST>
-__device__ __forceinline__ void fdct8(int d[8]) {
-    constexpr int S = FIRST ? 11 : 15, R = 1 << (S - 1);
-    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
-    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    if (FIRST) {
-        d[0] = (t10 + t11) << 2, d[4] = (t10 - t11) << 2;
-    } else {
-        d[0] = (t10 + t11 + 2) >> 2, d[4] = (t10 - t11 + 2) >> 2;
-    }
-    const int e1 = mad24(t12 + t13, 4433, R);
-    d[2] = mad24(t13, 6270, e1) >> S;
-    d[6] = mad24(t12, -15137, e1) >> S;
-    const int z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const int z5 = mad24(z3 + z4, 9633, R);
-    const int z3p = mad24(z3, -16069, z5), z4p = mad24(z4, -3196, z5);
-    const int a1 = mul24(z1, -7373), a2 = mul24(z2, -20995);
-    d[7] = mad24(t4, 2446, a1 + z3p) >> S;
-    d[5] = mad24(t5, 16819, a2 + z4p) >> S;
-    d[3] = mad24(t6, 25172, a2 + z3p) >> S;
-    d[1] = mad24(t7, 12299, a1 + z4p) >> S;
-}
-
-// jcdctmgr.c: (|c| + 4 q) / (8 q) = ((|c| + 4 q) >> 3) / q, the division as a multiply by
-// m = ceil(2^20 / q): exact for |c| + 4 q < 2^15 (the test walks every q and numerator)
-__device__ __forceinline__ int quantise(int c, uint32_t e) {
-    const uint32_t q = e >> 21, m = e & 0x1fffffu;
-    const uint32_t n = (static_cast<uint32_t>(c < 0 ? -c : c) + 4u * q) >> 3;
-    const int v = static_cast<int>(__umul24(n, m) >> kJpegcRecipShift);
-    return c < 0 ? -v : v;
-}
 
 // Where block `blk` of strip (sx, sy) goes in the image's output, in bytes; kNoBlock for a block
 // outside the real ones (the entropy coder's dummy blocks).  *chroma: which table quantises it.
@@ -169,52 +85,7 @@ __global__ void __launch_bounds__(256) k_jpegc(const JpegcArgs a) {
     if (tid < 128u) recips[tid] = a.recips[tid];
 
     // ---- A: pixels -> samples - 128 in LDS
-    {
-        const uint32_t g = tid & 31u, r = tid >> 5;  // group of 4 columns; row (4:4:4) or row pair (4:2:0)
-        const uint32_t x0 = sx * 128u + 4u * g;
-        const uint32_t row_bytes = 3u * a.w;
-        uint32_t d[3];
-        int y[4], cb[4], cr[4];
-        if (LAYOUT == MIPX_YCC_444) {
-            if (x0 < 8u * a.ywb) {
-                const uint32_t py = min(sy * 8u + r, a.h - 1u);
-                load_rgb4(in + py * row_bytes, x0, a.w, d);
-                rgb_ycc4(d, y, cb, cr);
-                int16_t *s = blocks + (g >> 1) * kBlockPitch + r * 8u + (g & 1u) * 4u;
-                put4(s, y);
-                put4(s + 16 * kBlockPitch, cb);
-                put4(s + 32 * kBlockPitch, cr);
-            }
-        } else if (x0 < 16u * a.cwb) {
-            const uint32_t j = sy * 8u + r;  // the image's row pair
-            const uint32_t y0 = min(2u * j, a.h - 1u), y1 = min(2u * j + 1u, a.h - 1u);
-            int sb[2], sr[2];
-            uint32_t d1[3];
-            load_rgb4(in + y0 * row_bytes, x0, a.w, d);
-            load_rgb4(in + y1 * row_bytes, x0, a.w, d1);
-            int16_t *s = blocks + ((r >> 2) * 16u + (g >> 1)) * kBlockPitch + (2u * r & 7u) * 8u + (g & 1u) * 4u;
-            rgb_ycc4(d, y, cb, cr);
-            put4(s, y);
-            sb[0] = cb[0] + cb[1], sb[1] = cb[2] + cb[3], sr[0] = cr[0] + cr[1], sr[1] = cr[2] + cr[3];
-            rgb_ycc4(d1, y, cb, cr);
-            put4(s + 8, y);
-            sb[0] += cb[0] + cb[1], sb[1] += cb[2] + cb[3], sr[0] += cr[0] + cr[1], sr[1] += cr[2] + cr[3];
-            if (j >= a.ch) {  // below the last chroma row: its rows again, not the repeated pixel row
-                const uint32_t c0 = 2u * a.ch - 2u, c1 = min(c0 + 1u, a.h - 1u);
-                load_rgb4(in + c0 * row_bytes, x0, a.w, d);
-                load_rgb4(in + c1 * row_bytes, x0, a.w, d1);
-                rgb_ycc4(d, y, cb, cr);
-                sb[0] = cb[0] + cb[1], sb[1] = cb[2] + cb[3], sr[0] = cr[0] + cr[1], sr[1] = cr[2] + cr[3];
-                rgb_ycc4(d1, y, cb, cr);
-                sb[0] += cb[0] + cb[1], sb[1] += cb[2] + cb[3], sr[0] += cr[0] + cr[1], sr[1] += cr[2] + cr[3];
-            }
-            // the lane's chroma columns are 2 g (even: bias 1) and 2 g + 1 (odd: bias 2)
-            int16_t *c = blocks + (32u + (g >> 2)) * kBlockPitch + r * 8u + (g & 3u) * 2u;
-            *reinterpret_cast<uint32_t *>(c) = pack16(((sb[0] + 1) >> 2) - 128, ((sb[1] + 2) >> 2) - 128);
-            *reinterpret_cast<uint32_t *>(c + 8 * kBlockPitch) =
-                pack16(((sr[0] + 1) >> 2) - 128, ((sr[1] + 2) >> 2) - 128);
-        }
-    }
+    strip_samples<LAYOUT>(blocks, in, a.w, a.h, a.ywb, a.cwb, a.ch, sx, sy);
     __syncthreads();
 
     // the lane's two (block, row / column) tasks: 384 over 256 threads
@@ -233,17 +104,7 @@ __global__ void __launch_bounds__(256) k_jpegc(const JpegcArgs a) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         if (off[i] == kNoBlock) continue;
-        uint4 *p = reinterpret_cast<uint4 *>(blk[i] + line[i] * 8u);
-        const uint4 v = *p;
-        const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-        int d[8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            d[2 * k] = static_cast<int>(u[k] << 16) >> 16;
-            d[2 * k + 1] = static_cast<int>(u[k]) >> 16;
-        }
-        fdct8<true>(d);
-        *p = make_uint4(pack16(d[0], d[1]), pack16(d[2], d[3]), pack16(d[4], d[5]), pack16(d[6], d[7]));
+        fdct8_row(blk[i], line[i]);
     }
     __syncthreads();
 

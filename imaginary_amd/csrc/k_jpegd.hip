@@ -37,11 +37,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "jpeg_dct.h"
 
 namespace mipx {
 namespace {
 
 using namespace dev;
+using namespace jidct;
 
 struct JpegdArgs {
     const u8 *in;
@@ -57,60 +59,6 @@ struct JpegdArgs {
 };
 
 constexpr int kRun = 32;         // blocks of one workgroup; 8 lanes per block
-constexpr int kBlockPitch = 72;  // int16s between blocks in LDS: 64 + 8 (k_jpegc.hip)
-
-typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
-
-// a * k + c and a * k modulo 2^32, with 24-bit signed a and k: the full-rate v_mad_i32_i24 /
-// v_mul_i32_i24 (k_jpegc.hip)
-__device__ __forceinline__ uint32_t mad24(int a, int k, uint32_t c) {
-    uint32_t r;
-    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(k), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t mul24(int a, int k) {
-    uint32_t r;
-    asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "s"(k), "v"(a));
-    return r;
-}
-
-// the low 16 bits of both 16-bit products (v_pk_mul_lo_u16): signed or not, they are the same
-__device__ __forceinline__ uint32_t dequant2(uint32_t coefs, uint32_t q) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(ushort2v, coefs) * __builtin_bit_cast(ushort2v, q));
-}
-
-__device__ __forceinline__ int descale(uint32_t v, int s) { return static_cast<int>(v) >> s; }
-
-// One 8-point pass of jidctint.c in place, |i| <= 2^15.  Sums are unsigned, so they wrap; the
-// rounding constant of the descale rides in t0 and t1, which every output contains once.
-template <int S>
-__device__ __forceinline__ void idct8(int i[8]) {
-    constexpr uint32_t R = 1u << (S - 1);
-    const uint32_t e1 = mul24(i[2] + i[6], 4433);
-    const uint32_t t2 = mad24(i[6], -15137, e1), t3 = mad24(i[2], 6270, e1);
-    const uint32_t t0 = (static_cast<uint32_t>(i[0] + i[4]) << 13) + R;
-    const uint32_t t1 = (static_cast<uint32_t>(i[0] - i[4]) << 13) + R;
-    const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    const int z1 = i[7] + i[1], z2 = i[5] + i[3], z3 = i[7] + i[3], z4 = i[5] + i[1];
-    const uint32_t z5 = mul24(z3 + z4, 9633);
-    const uint32_t z3p = mad24(z3, -16069, z5), z4p = mad24(z4, -3196, z5);
-    const uint32_t m1 = mul24(z1, -7373), m2 = mul24(z2, -20995);
-    const uint32_t a0 = mad24(i[7], 2446, m1 + z3p), a1 = mad24(i[5], 16819, m2 + z4p);
-    const uint32_t a2 = mad24(i[3], 25172, m2 + z3p), a3 = mad24(i[1], 12299, m1 + z4p);
-    i[0] = descale(t10 + a3, S), i[7] = descale(t10 - a3, S);
-    i[1] = descale(t11 + a2, S), i[6] = descale(t11 - a2, S);
-    i[2] = descale(t12 + a1, S), i[5] = descale(t12 - a1, S);
-    i[3] = descale(t13 + a0, S), i[4] = descale(t13 - a0, S);
-}
-
-// clamp(v + 128, 0, 255).  The asm barrier keeps the backend from fusing shift + clamp + byte
-// packing into v_ashr_pk_u8_i32 with the next byte ORed into its unwritten half (k_sep.hip
-// fixed_round_i).
-__device__ __forceinline__ uint32_t sample(int v) {
-    int s = clampi(v + 128, 0, 255);
-    asm("" : "+v"(s));
-    return static_cast<uint32_t>(s);
-}
 
 __global__ void __launch_bounds__(256) k_jpegd(const JpegdArgs a) {
     __shared__ __attribute__((aligned(16))) int16_t blocks[kRun * kBlockPitch];
@@ -268,39 +216,6 @@ struct JpegdsArgs {
 
 constexpr int kMaxRun = 128;     // N = 2
 constexpr int kDcPerLane = 4;    // N = 1: blocks of one lane
-
-template <int N>
-__device__ __forceinline__ constexpr bool idct_reads(uint32_t k) {
-    return N == 8 || (N == 4 && k != 4u) || (N == 2 && (k == 0u || (k & 1u)));
-}
-
-// One pass of jidctred.c's 4 x 4 inverse DCT: i[0..3] from i[0 1 2 3 5 6 7]; the rounding
-// constant rides in t0
-template <int S>
-__device__ __forceinline__ void idct4(int i[8]) {
-    const uint32_t t0 = (static_cast<uint32_t>(i[0]) << 14) + (1u << (S - 1));
-    const uint32_t t2 = mad24(i[6], -6270, mul24(i[2], 15137));
-    const uint32_t t10 = t0 + t2, t12 = t0 - t2;
-    const uint32_t a0 = mad24(i[1], 8697, mad24(i[3], -17799, mad24(i[5], 11893, mul24(i[7], -1730))));
-    const uint32_t a2 = mad24(i[1], 20995, mad24(i[3], 7373, mad24(i[5], -4926, mul24(i[7], -4176))));
-    i[0] = descale(t10 + a2, S), i[3] = descale(t10 - a2, S);
-    i[1] = descale(t12 + a0, S), i[2] = descale(t12 - a0, S);
-}
-
-// ... and of its 2 x 2 one: i[0..1] from i[0 1 3 5 7]
-template <int S>
-__device__ __forceinline__ void idct2(int i[8]) {
-    const uint32_t t10 = (static_cast<uint32_t>(i[0]) << 15) + (1u << (S - 1));
-    const uint32_t t0 = mad24(i[1], 29692, mad24(i[3], -10426, mad24(i[5], 6967, mul24(i[7], -5906))));
-    i[0] = descale(t10 + t0, S), i[1] = descale(t10 - t0, S);
-}
-
-template <int N, int PASS>
-__device__ __forceinline__ void idctn(int i[8]) {
-    if constexpr (N == 8) idct8<PASS == 1 ? 11 : 18>(i);
-    if constexpr (N == 4) idct4<PASS == 1 ? 12 : 19>(i);
-    if constexpr (N == 2) idct2<PASS == 1 ? 13 : 20>(i);
-}
 
 // A run of 256 / N blocks of block row `by`, from block bx0, of a component whose coefficients
 // start at `coefs` and whose table is `qt`; `plane` is its output plane

@@ -207,6 +207,10 @@ int jpegd_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int la
 // the same payload of a w x h file at 1/shrink (2, 4, 8) -> three planes of ceil(w / shrink) x ceil(h / shrink),
 // packed as MIPX_YCC_444
 int jpegds_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, int shrink, hipStream_t st);
+// k_jpegrt.hip: RGB -> the planes ycc_launch takes of the JPEG of each image at `quality`, decoded at 1/shrink
+// (1, 2, 4, 8): packed as `layout` at full size, as three ceil(w / shrink) x ceil(h / shrink) planes otherwise
+int jpegrt_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, int quality, int shrink,
+                  hipStream_t st);
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,

@@ -24,6 +24,12 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
         // the decoded planes between the inverse DCT and the upsample + conversion, packed as
         // mipx_ycc_bytes; sized by the 4:4:4 bound, which needs no layout
         case MIPX_OP_JPEGD: return align_up(static_cast<size_t>(n) * w * h * 3);
+        // the round trip's planes between its two launches: p0 = shrink (0 or 1: full size), three
+        // planes of the decoded size at most
+        case MIPX_OP_JPEGRT: {
+            const size_t s = p0 > 1.0 ? static_cast<size_t>(p0) : 1;
+            return align_up(static_cast<size_t>(n) * ((w + s - 1) / s) * ((h + s - 1) / s) * 3);
+        }
         default: return 0;
     }
 }
@@ -199,6 +205,32 @@ int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, 
     const int e = jpegds_launch(d_in, planes, n, file_w, file_h, layout, shrink, as_stream(stream));
     if (e) return e;
     return ycc_launch(planes, d_out, n, ow, oh, MIPX_YCC_444, as_stream(stream));
+}
+
+int mipx_op_jpeg_roundtrip(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
+                           int32_t quality, int32_t shrink, void *d_ws, size_t ws_bytes, void *stream) {
+    if (shrink == 0) shrink = 1;
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
+        quality < 1 || quality > 100 || (shrink != 1 && shrink != 2 && shrink != 4 && shrink != 8))
+        return MIPX_EINVAL;
+    // byte offsets inside an image are 32-bit in both kernels
+    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+        set_error("jpeg round trip: image %dx%d too large (an image's bytes >= 2^32)", w, h);
+        return MIPX_EUNSUPPORTED;
+    }
+    const size_t need = op_workspace_bytes(MIPX_OP_JPEGRT, n, w, h, 3, shrink, 0);
+    if (!d_ws || ws_bytes < need) {
+        set_error("jpeg round trip: workspace %zu < %zu bytes", ws_bytes, need);
+        return MIPX_EINVAL;
+    }
+    uint8_t *planes = static_cast<uint8_t *>(d_ws);
+    const int e = jpegrt_launch(d_in, planes, n, w, h, layout, quality, shrink, as_stream(stream));
+    if (e) return e;
+    // full-size 4:2:0 keeps its half-size chroma planes for the fancy upsample; every other case made
+    // three equal planes of the decoded size
+    if (shrink == 1) return ycc_launch(planes, d_out, n, w, h, layout, as_stream(stream));
+    return ycc_launch(planes, d_out, n, (w + shrink - 1) / shrink, (h + shrink - 1) / shrink, MIPX_YCC_444,
+                      as_stream(stream));
 }
 
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t bands, double xscale,

@@ -544,6 +544,7 @@ namespace {
 int textmark_index(const mipx_plan *p) {
     int i = p->n_steps;
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_JPEGC) --i;  // the coefficients are made of the marked image
+    if (i > 0 && p->steps[i - 1].op == MIPX_OP_JPEGRT) --i;  // ... and so is the re-encoded one
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_BW) --i;
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_FLATTEN) --i;
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_WATERMARK) --i;
@@ -698,6 +699,47 @@ extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32
     s.op = MIPX_OP_JPEGC;
     s.a[0] = layout, s.a[1] = quality;
     s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
+    return MIPX_OK;
+}
+
+// ---- JPEG round trip (MIPX_OP_JPEGRT) ------------------------------------------------
+extern "C" int mipx_plan_add_jpeg_roundtrip(mipx_plan *plan, int32_t layout, int32_t quality, int32_t shrink) {
+    const char *who = "mipx_plan_add_jpeg_roundtrip";
+    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (quality < 1 || quality > 100) {
+        mipx::set_error("%s: quality %d outside 1..100", who, quality);
+        return MIPX_EINVAL;
+    }
+    if (shrink != 0 && shrink != 1 && shrink != 2 && shrink != 4 && shrink != 8) {
+        mipx::set_error("%s: shrink %d is not 1, 2, 4 or 8", who, shrink);
+        return MIPX_EINVAL;
+    }
+    if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
+        mipx::set_error("%s: the plan makes %dx%dx%d, a YCbCr JPEG is of 3 bands", who, plan->out_w, plan->out_h,
+                        plan->out_bands);
+        return MIPX_EINVAL;
+    }
+    if (mipx_jpegd_bytes(plan->out_w, plan->out_h, layout) > 0xffffffffull ||
+        3ull * plan->out_w * plan->out_h > 0xffffffffull) {
+        mipx::set_error("%s: a %dx%d image's coefficients or RGB are 2^32 bytes or more", who, plan->out_w,
+                        plan->out_h);
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps > 0 && plan->steps[plan->n_steps - 1].op == MIPX_OP_JPEGC) {
+        mipx::set_error("%s: the plan already gives coefficients", who);
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps >= MIPX_MAX_STEPS) {
+        mipx::set_error("%s: the plan is full (MIPX_MAX_STEPS)", who);
+        return MIPX_EINVAL;
+    }
+    const int32_t s1 = shrink > 1 ? shrink : 1;
+    mipx_step &s = plan->steps[plan->n_steps++];
+    std::memset(&s, 0, sizeof(s));
+    s.op = MIPX_OP_JPEGRT;
+    s.a[0] = layout, s.a[1] = quality, s.a[2] = shrink;
+    s.out_w = (plan->out_w + s1 - 1) / s1, s.out_h = (plan->out_h + s1 - 1) / s1, s.out_bands = 3;
+    plan->out_w = s.out_w, plan->out_h = s.out_h;
     return MIPX_OK;
 }
 

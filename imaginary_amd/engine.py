@@ -11,13 +11,14 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, YCC_444, YCC_420, sync_tuning)
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, YCC_444, YCC_420, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
            "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420",
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
+           "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -361,6 +362,15 @@ def plan_set_jpegc_output(plan: MipxPlan, layout: int, quality: int) -> MipxPlan
     return plan
 
 
+def plan_add_jpeg_roundtrip(plan: MipxPlan, layout: int, quality: int, shrink: int = 1) -> MipxPlan:
+    """mipx_plan_add_jpeg_roundtrip on `plan` (in place; returned for convenience): the plan's
+    3-band result then goes through a JPEG of itself (YCC_444 or YCC_420, made at `quality`)
+    decoded at 1/shrink (1, 2, 4, 8), as a re-encode and decode on the host would leave it; more
+    steps, a text watermark and plan_set_jpegc_output may follow."""
+    check(lib.mipx_plan_add_jpeg_roundtrip(C.byref(plan), layout, quality, shrink), "mipx_plan_add_jpeg_roundtrip")
+    return plan
+
+
 def _jpegc_layout(plan: MipxPlan):
     """The layout of the coefficients a plan gives, or None for interleaved pixels."""
     last = plan.steps[plan.n_steps - 1] if plan.n_steps > 0 else None
@@ -429,7 +439,8 @@ class Engine:
         elif out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
             raise ValueError(f"out must be contiguous {np.dtype(dtype).name} {shape}")
         ti = C.c_uint64()
-        wmi = C.byref(_img(np.ascontiguousarray(wm, dtype=np.uint8))) if wm is not None else None
+        wm = np.ascontiguousarray(wm, dtype=np.uint8) if wm is not None else None  # a copy must live until the submit
+        wmi = C.byref(_img(wm)) if wm is not None else None
         src = MipxImg(img.ctypes.data, plan.in_w, plan.in_h, 3, 0) if planar else _img(img)
         dst = MipxImg(out.ctypes.data, plan.out_w, plan.out_h, 3, 0) if coefs is not None else _img(out)
         check(lib.mipx_submit(device, C.byref(plan), C.byref(src), wmi, C.byref(dst),
@@ -649,6 +660,27 @@ def jpegd_to_rgb_scaled(payload: np.ndarray, w: int, h: int, layout: int, shrink
     wsb = lib.mipx_op_workspace_bytes(OP_JPEGD, n, ow, oh, 3, 0.0, 0.0)
     ws = _dev("ws", what, wsb)
     check(lib.mipx_op_jpegd_to_rgb_scaled(din.ptr, dout.ptr, n, w, h, layout, shrink, ws.ptr, wsb, None), what)
+    synchronize()
+    _check_guards(what, din, dout, ws)
+    return dout.download((n, oh, ow, 3))
+
+
+def jpeg_roundtrip(imgs: np.ndarray, layout: int, quality: int, shrink: int = 1) -> np.ndarray:
+    """mipx_op_jpeg_roundtrip on (h, w, 3) or (n, h, w, 3) uint8: the pixels the JPEG of each image
+    at `quality` decodes to at 1/shrink; returns (n, ceil(h / shrink), ceil(w / shrink), 3)."""
+    sync_tuning()
+    x = _batch(imgs)
+    n, h, w, b = x.shape
+    if b != 3 or layout not in (YCC_444, YCC_420) or shrink not in (1, 2, 4, 8):
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout} at 1/{shrink}: RGB, YCC_444 / YCC_420, "
+                         f"shrink 1, 2, 4 or 8")
+    ow, oh = -(-w // shrink), -(-h // shrink)
+    what = "mipx_op_jpeg_roundtrip"
+    din = _dev("in", what, x.nbytes, w * 3, x)
+    dout = _dev("out", what, n * oh * ow * 3, ow * 3)
+    wsb = lib.mipx_op_workspace_bytes(OP_JPEGRT, n, w, h, 3, float(shrink), 0.0)
+    ws = _dev("ws", what, wsb)
+    check(lib.mipx_op_jpeg_roundtrip(din.ptr, dout.ptr, n, w, h, layout, quality, shrink, ws.ptr, wsb, None), what)
     synchronize()
     _check_guards(what, din, dout, ws)
     return dout.download((n, oh, ow, 3))

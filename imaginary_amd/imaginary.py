@@ -28,8 +28,8 @@ from typing import Any, Callable, Dict, List, Optional
 import numpy as np
 
 from . import _abi, codec
-from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_textmark, plan_chain, plan_make,
-                     plan_set_jpegc_output, plan_set_jpegd_input, plan_set_jpegd_input_scaled, plan_set_ycc_input, plan_textmark_geometry)
+from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_jpeg_roundtrip, plan_add_textmark,
+                     plan_chain, plan_make, plan_set_jpegc_output, plan_set_jpegd_input, plan_set_jpegd_input_scaled, plan_set_ycc_input, plan_textmark_geometry)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -517,6 +517,8 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     results of other band counts come back as pixels."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         return process_bytes(bytes(img), opts, wm, text)
+    if isinstance(img, _Staged):
+        return _plan_stage(img, opts, wm, text)
     opts = {k: v for k, v in opts.items() if k not in _ENCODE_ONLY}
     px = img.pixels if img.pixels.ndim == 3 else img.pixels[:, :, None]
     inp = make_input(img.w, img.h, px.shape[2], img.type, img.orientation)
@@ -570,7 +572,7 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
-                  jpeg_dct_shrink: bool = False) -> Image:
+                  jpeg_dct_shrink: bool = False, device_reencode: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -587,7 +589,10 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     `ycc`'s when that is set too: of the two, jpeg_dct is tried first.
     jpeg_dct_shrink: with jpeg_dct, a shrink-on-load request that does not rotate goes to the engine as
     coefficients too, decoded there at the scale codec.decode(buf, shrink) would deliver; the bytes
-    are the same either way."""
+    are the same either way.
+    device_reencode: a 3-band JPEG that rotates and shrinks on load (_rotate_reencode_shrink_on_load)
+    runs as one plan, the re-encode and the scaled decode as a MIPX_OP_JPEGRT step between the
+    rotation and the rest: one upload, no host codec in between; the bytes are the same either way."""
     opts = dict(opts)
     out_type = str(opts.pop("type", "") or "")
     quality = int(opts.pop("quality", 0) or 0)
@@ -619,7 +624,7 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         raise ImaginaryError(f"image processing error: {e}", 500) from e
     rotates = any(step[0] in ("rot", "flip") for step in plan.describe())
     if plan.load_shrink > 1 and itype == "jpeg" and rotates and not opts.get("no_auto_rotate"):
-        px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text)
+        px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text, device=device_reencode)
     elif plan.load_shrink > 1:  # process() re-plans on the codec-shrunk size
         take = jpeg_dct and jpeg_dct_shrink and hdr.bands == 3 and itype == "jpeg" and not rotates
         dct = codec.decode_jpeg_coefs(buf) if take else None
@@ -641,6 +646,11 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     if isinstance(px, JpegCoefs):
         body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)
         return Image(body, codec.mime_type(codec.sniff_type(body)))
+    return _encode(px, t, quality, compression)
+
+
+def _encode(px: np.ndarray, t: str, quality: int, compression) -> Image:
+    """The encode that ends process_bytes: WEBP/HEIF/AVIF failures retry as JPEG (image.go:97-107)."""
     try:
         body = codec.encode(px, t, quality or None, compression)
     except codec.CodecError as e:
@@ -665,8 +675,43 @@ def _drop_leading_steps(plan, k: int, w: int, h: int):
     return rest
 
 
+def _rotated_shrink_plan(w: int, h: int, itype: str, orientation: int, opts: Dict[str, Any], wm_px,
+                         text: Optional[TextMark] = None):
+    """_rotate_reencode_shrink_on_load as ONE plan on the full-size w x h x 3 decode: the rotation
+    steps, the re-encode at Q 100 (4:4:4, as codec.encode samples from Q 90) and its decode at the
+    scale the host codec would deliver as a MIPX_OP_JPEGRT step, then the rest of the plan on that
+    size.  Returns (plan, watermark pixels)."""
+    rot_opts = {k: opts[k] for k in _ROTATION_KEYS if k in opts}
+    rot_plan = plan_make(make_opts(**rot_opts), make_input(w, h, 3, "png", orientation))
+    rot_ops = [step[0] for step in rot_plan.describe()]
+    if not rot_ops or any(op not in ("rot", "flip") for op in rot_ops):
+        raise ImaginaryError(f"rotation plan {rot_ops}: expected rot / flip steps only", 500)
+    inp = make_input(w, h, 3, itype, orientation)
+    if wm_px is not None:
+        wm_px = wm_px if wm_px.ndim == 3 else wm_px[:, :, None]
+        opts = dict(opts, wm_enable=1)
+        inp.wm_w, inp.wm_h, inp.wm_bands = wm_px.shape[1], wm_px.shape[0], wm_px.shape[2]
+    plan = plan_make(make_opts(**opts), inp)
+    uw, uh = rot_plan.out_w, rot_plan.out_h
+    scale = codec.decode_scale(uw, uh, plan.load_shrink)
+    dw, dh = -(-uw // scale), -(-uh // scale)
+    # the decode the plan was made for is the un-rotated image at 1/s: same size, axes swapped
+    # by a quarter turn
+    inp.decoded_w, inp.decoded_h = (dh, dw) if (uh, uw) != (h, w) else (dw, dh)
+    plan = plan_make(make_opts(**opts), inp)
+    if text is not None:
+        wm_px = _add_textmark(plan, text)
+    steps = plan.describe()
+    k = len(rot_ops)
+    if [st[0] for st in steps[:k]] != rot_ops:
+        raise ImaginaryError(f"plan {steps}: expected the rotation steps {rot_ops} first", 500)
+    plan_add_jpeg_roundtrip(rot_plan, codec.YCC_444, JPEG_REENCODE_QUALITY, scale)
+    rest = _drop_leading_steps(plan, k, dw, dh)
+    return (plan_chain([rot_plan, rest]) if rest.n_steps else rot_plan), wm_px
+
+
 def _rotate_reencode_shrink_on_load(buf: bytes, hdr, itype: str, opts: Dict[str, Any], wm_px,
-                                    text: Optional[TextMark] = None):
+                                    text: Optional[TextMark] = None, device: bool = False):
     """bimg 1.1.9 resizer() for a JPEG that rotates or flips (EXIF orientation or an
     explicit rotate / flip / flop) and then shrinks on load (image.go:96 -> bimg
     resizer.go): rotateAndFlipImage runs on the FULL-size decode, the rotated image is
@@ -677,8 +722,18 @@ def _rotate_reencode_shrink_on_load(buf: bytes, hdr, itype: str, opts: Dict[str,
       2. rotate / flip on the engine (the plan's rotation steps, at full size);
       3. re-encode with the host codec (JPEG Q 100, no EXIF);
       4. decode that with the DCT shrink the plan asks for;
-      5. run the rest of the plan on it."""
+      5. run the rest of the plan on it.
+    device: steps 2 to 5 as one plan, 3 and 4 as its MIPX_OP_JPEGRT step (_rotated_shrink_plan);
+    3-band files only, the others keep the host codec."""
     full = codec.decode(buf)
+    if device and full.shape[2] == 3:
+        try:
+            plan, wm_px = _rotated_shrink_plan(full.shape[1], full.shape[0], itype, hdr.orientation, opts, wm_px, text)
+        except _abi.MipxError as e:
+            if e.code == _abi.MIPX_EUNSUPPORTED:
+                raise EngineUnsupported(str(e)) from e
+            raise ImaginaryError(f"image processing error: {e}", 500) from e
+        return _run(plan, full, wm_px)
     rot_opts = {k: opts[k] for k in _ROTATION_KEYS if k in opts}
     rot_plan = plan_make(make_opts(**rot_opts), make_input(full.shape[1], full.shape[0], full.shape[2], "png",
                                                            hdr.orientation))
@@ -897,15 +952,120 @@ def _stage_kw(fn, kw):
     return {k: v for k, v in kw.items() if k not in ("wm", "render") or k == keep}
 
 
-def Pipeline(img, o: ImageOptions, **kw):
+@dataclass
+class _Staged:
+    """An encoded image of the fused pipeline that a stage plans on instead of decoding: the
+    header facts process_bytes would read from it, and the list the stages' plans collect in.
+    Only the pipeline's first file exists (`buf`); the intermediates never do."""
+    type: str
+    w: int
+    h: int
+    bands: int
+    orientation: int
+    stages: list
+    buf: Optional[bytes] = None
+
+
+def _plan_stage(img: _Staged, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None) -> _Staged:
+    """process_bytes up to the engine run, for one stage of the fused pipeline: plans the stage as
+    process_bytes would on a file with img's header, appends what the chain needs to img.stages
+    and returns the header of the file the stage would have written.
+      plan: the stage's steps on the image the engine has at that point;
+      shrink: the scale the file in front of the stage decodes at (the boundary's round trip does it);
+      px: the host decode of the first file (stage 0 only);
+      t, quality, compression: how the stage's result is encoded."""
+    opts = dict(opts)
+    out_type = str(opts.pop("type", "") or "")
+    quality = int(opts.pop("quality", 0) or 0)
+    compression = opts.pop("compression", 0) or None
+    wm_px = codec.decode(bytes(wm)) if isinstance(wm, (bytes, bytearray)) else wm
+    t = out_type or img.type
+    if wm_px is not None:
+        wm_px = wm_px if wm_px.ndim == 3 else wm_px[:, :, None]
+        opts = dict(opts, wm_enable=1)
+    inp = make_input(img.w, img.h, img.bands, img.type, img.orientation)
+    if wm_px is not None:
+        inp.wm_w, inp.wm_h, inp.wm_bands = wm_px.shape[1], wm_px.shape[0], wm_px.shape[2]
+    plan = plan_make(make_opts(**opts), inp)
+    rotates = any(step[0] in ("rot", "flip") for step in plan.describe())
+    px, shrink = None, 1
+    if plan.load_shrink > 1 and img.type == "jpeg" and rotates and not opts.get("no_auto_rotate"):
+        if img.bands != 3:
+            raise EngineUnsupported("the fused pipeline re-encodes 3-band images only")
+        px = codec.decode(img.buf) if img.buf is not None else None
+        plan, wm_px = _rotated_shrink_plan(img.w, img.h, img.type, img.orientation, opts, wm_px, text)
+    else:
+        if plan.load_shrink > 1:  # re-plan on the size the codec delivers, as process() does
+            shrink = codec.decode_scale(img.w, img.h, plan.load_shrink)
+            inp.decoded_w, inp.decoded_h = -(-img.w // shrink), -(-img.h // shrink)
+            plan = plan_make(make_opts(**opts), inp)
+            plan.load_shrink = 1  # the decode is not the engine's: stage 0's is the host's, later ones the boundary's
+        if img.buf is not None:
+            px = codec.decode(img.buf, shrink)
+            if (px.shape[1], px.shape[0]) != (plan.in_w, plan.in_h):
+                raise ImaginaryError("decoded size does not match the plan", 500)
+        if text is not None:
+            wm_px = _add_textmark(plan, text)
+    img.stages.append(dict(plan=plan, wm=wm_px, shrink=shrink, px=px, t=t, quality=quality, compression=compression))
+    return _Staged(t, plan.out_w, plan.out_h, plan.out_bands, 0, img.stages)
+
+
+def _pipeline_fused(buf: bytes, o: ImageOptions, kw) -> Optional[Image]:
+    """Pipeline over encoded bytes as one engine run: the first file is decoded once, every stage
+    is planned on the file the stage before it would have written, a JPEG boundary becomes a
+    MIPX_OP_JPEGRT step at the boundary's quality and sampling (and at the scale the next stage
+    would shrink on load at), a PNG boundary nothing, and the chain runs as one plan with one
+    upload and one download; the last stage is encoded as process_bytes does.  None when the
+    pipeline is not one the chain can stand for; the caller then runs stage by stage."""
+    try:
+        hdr = codec.header(buf)
+    except codec.CodecError:
+        return None
+    if hdr.type not in ("jpeg", "png"):
+        return None
+    stages: list = []
+    cur = _Staged(hdr.type, hdr.w, hdr.h, hdr.bands, hdr.orientation, stages, buf)
+    try:
+        for op in o.operations:
+            fn = OperationsMap.get(op.get("operation") or op.get("name"))
+            if fn is None:
+                return None
+            if stages and (cur.type not in ("jpeg", "png") or cur.bands != 3):
+                return None   # an intermediate the engine cannot stand in for
+            cur = fn(cur, build_params_from_operation(op), **_stage_kw(fn, kw))
+        plans = []
+        for k, st in enumerate(stages):
+            if k + 1 < len(stages) and st["t"] == "jpeg":
+                q = st["quality"] or codec.DEFAULT_QUALITY
+                plan_add_jpeg_roundtrip(st["plan"], codec.YCC_444 if q >= 90 else codec.YCC_420, q, stages[k + 1]["shrink"])
+            elif k + 1 < len(stages) and stages[k + 1]["shrink"] != 1:
+                return None
+            plans.append(st["plan"])
+        merged = plan_chain(plans)
+        wms = [st["wm"] for st in stages if st["wm"] is not None]
+        px = _run(merged, stages[0]["px"], wms[0] if wms else None)
+    except (ImaginaryError, _abi.MipxError, codec.CodecError):
+        return None   # a stage that fails, a chain the planner refuses: today's loop decides
+    last = stages[-1]
+    return _encode(px, last["t"], last["quality"], last["compression"])
+
+
+def Pipeline(img, o: ImageOptions, fused: bool = False, **kw):
     """image.go:379-410.  On encoded bytes every stage decodes and re-encodes in
     the stage's output format, exactly as the reference; on a Decoded input the
-    intermediates stay pixels (lossless, as PNG intermediates would be)."""
+    intermediates stay pixels (lossless, as PNG intermediates would be).
+    fused (encoded bytes only): run the stages as one plan on the engine, the JPEG re-encodes
+    between them as MIPX_OP_JPEGRT steps (_pipeline_fused); the bytes are the same, and a
+    pipeline the chain cannot stand for runs stage by stage as without the flag."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         if len(o.operations) == 0:
             raise ImaginaryError("Missing pipeline operations")
         if len(o.operations) > 10:
             raise ImaginaryError("Maximum pipeline operations (10) exceeded")
+        if fused:
+            done = _pipeline_fused(bytes(img), o, kw)
+            if done is not None:
+                return done
         out = Image(bytes(img), codec.mime_type(codec.sniff_type(img)))
         for op in o.operations:
             name = op.get("operation") or op.get("name")

@@ -141,7 +141,7 @@ enum {
                             bands; the output buffer is then the quantised coefficients
                             (mipx_plan_set_jpegc_output)
                                   (libjpeg colour conversion, downsample, forward DCT, quantisation) */
-    MIPX_OP_JPEGD        /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, never together
+    MIPX_OP_JPEGD,       /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, never together
                             with MIPX_OP_YCC; the input buffer is then the file's quantisation tables and
                             quantised coefficients (mipx_plan_set_jpegd_input)
                                   (libjpeg dequantisation, inverse DCT, upsample, colour conversion)
@@ -150,6 +150,11 @@ enum {
                             the payload is that file's, and the plan's in_w x in_h must be
                             ceil(a[2] / a[1]) x ceil(a[3] / a[1]) (mipx_plan_set_jpegd_input_scaled);
                             any other a[1] is MIPX_EINVAL */
+    MIPX_OP_JPEGRT       /* = 18, the JPEG round trip: a[0] = MIPX_YCC_*, a[1] = quality 1..100, a[2] = shrink
+                            (0 or 1 full size; 2, 4, 8); on a 3-band image at any index of a plan; out =
+                            ceil(w / shrink) x ceil(h / shrink) x 3: the pixels the JPEG of the image at that
+                            quality decodes to at that scale (mipx_plan_add_jpeg_roundtrip)
+                                  (MIPX_OP_JPEGC's rule, then MIPX_OP_JPEGD's with the same tables) */
 };
 
 /* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
@@ -194,6 +199,12 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * the output size and nothing is upsampled; the conversion is the 4:4:4 one.  Bit for bit
  * libjpeg-turbo's on files an encoder writes, tests/jpegds_ref.py's rule elsewhere
  * (PARITY_ASSUMPTIONS.md row 19). */
+/* JPEG round trip (MIPX_OP_JPEGRT): what re-encoding an image as a JPEG and decoding that file
+ * does to its pixels, as imaginary's /pipeline does between stages and bimg does before a rotated
+ * JPEG shrinks on load, without the file: exactly MIPX_OP_JPEGC's rule at (layout, quality), then
+ * exactly MIPX_OP_JPEGD's rule on those coefficients at scale 1 / shrink with the tables of
+ * jpeg_set_quality(quality, TRUE).  Blocks are independent, so the coefficients stay on the chip.
+ * Bit for bit libjpeg-turbo's encode -> decode (PARITY_ASSUMPTIONS.md row 20). */
 #define MIPX_JPEGD_HEADER_BYTES 384
 
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
@@ -248,7 +259,9 @@ int mipx_plan_make(const mipx_opts *opts, const mipx_input *in, mipx_plan *plan)
  * into one plan, so the request path runs the chain with one upload, device-resident
  * intermediates and one download.  Stage k > 0 must take stage k-1's output geometry
  * and have load_shrink 1; at most one stage may carry a watermark step (WATERMARK or
- * TEXTMARK: a request has one watermark image).
+ * TEXTMARK: a request has one watermark image).  A stage whose file the reference would
+ * write as a JPEG ends with MIPX_OP_JPEGRT (mipx_plan_add_jpeg_roundtrip), which also does
+ * the next stage's shrink-on-load.
  * MIPX_EUNSUPPORTED when the chain exceeds MIPX_MAX_STEPS or has two watermark stages
  * (the caller then runs the stages one by one). */
 int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out);
@@ -324,6 +337,17 @@ int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout);
  * 1, 2, 4, 8 and for a file size that does not give in_w x in_h at that shrink. */
 int mipx_plan_set_jpegd_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
                                      int32_t file_h);
+/* JPEG round trip (MIPX_OP_JPEGRT); works without a GPU.  Appends the step to a plan whose output
+ * has 3 bands; out_w x out_h become ceil(out_w / shrink) x ceil(out_h / shrink) (shrink 0 or 1:
+ * unchanged).  Input and output buffers stay pixels.  The step is legal at any index of a plan and
+ * in any stage of a mipx_plan_chain: a caller whose next stage shrinks on load puts that shrink
+ * into the step and plans the stage on the decoded size with load_shrink 1.
+ * mipx_plan_add_textmark on a plan that ends with the step inserts before it (the file is made of
+ * the marked image), and mipx_plan_set_jpegc_output may follow it.  MIPX_EINVAL, with the plan
+ * untouched, for an unknown layout, a quality outside 1..100, a shrink other than 0, 1, 2, 4, 8,
+ * out_bands != 3, an image whose coefficients or RGB are 2^32 bytes or more, a plan that ends with
+ * MIPX_OP_JPEGC, or a full plan. */
+int mipx_plan_add_jpeg_roundtrip(mipx_plan *plan, int32_t layout, int32_t quality, int32_t shrink);
 /* imaginary image.go:190 calculateDestinationFitDimension */
 int mipx_fit_dimension(int32_t image_w, int32_t image_h, int32_t fit_w, int32_t fit_h,
                        int32_t *out_w, int32_t *out_h);
@@ -421,6 +445,17 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
 int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t file_w, int32_t file_h,
                                 int32_t layout, int32_t shrink, void *d_workspace, size_t workspace_bytes,
                                 void *stream);
+/* n x h x w x 3 RGB -> n x oh x ow x 3 RGB with ow = ceil(w / shrink), oh = ceil(h / shrink)
+ * (shrink 0 = 1): the JPEG round trip (MIPX_OP_JPEGRT); both pointers at any alignment.  One launch
+ * makes the decoder's planes in the workspace, the MIPX_OP_YCC kernels make RGB of them:
+ * mipx_op_workspace_bytes(MIPX_OP_JPEGRT, n, w, h, 3, shrink, 0) bytes, the planes', at most 3 per
+ * input pixel.  MIPX_EINVAL, before any HIP call, for NULL pointers, n <= 0, a non-positive size,
+ * an unknown layout, a quality outside 1..100, a shrink other than 0, 1, 2, 4, 8 or a workspace
+ * that is NULL or too small; MIPX_EUNSUPPORTED for an image whose coefficients or RGB are 2^32
+ * bytes or more (the kernels' byte offsets inside an image are 32-bit). */
+int mipx_op_jpeg_roundtrip(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                           int32_t layout, int32_t quality, int32_t shrink, void *d_workspace,
+                           size_t workspace_bytes, void *stream);
 int mipx_op_affine(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                    int32_t bands, double xscale, double yscale, int32_t extend, void *stream);
 int mipx_op_zoom(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,

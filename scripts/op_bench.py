@@ -8,8 +8,9 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpegc420 --w 3840 --h 2160 --n 64 --q 75
     python scripts/op_bench.py jpegd420 --w 3840 --h 2160 --n 64 --q 75
     python scripts/op_bench.py jpegds420 --w 3840 --h 2160 --n 64 --q 75 --shrink 4
+    python scripts/op_bench.py jpegrt420 --w 3840 --h 2160 --n 64 --q 75
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
-         jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444
+         jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444 jpegrt420 jpegrt444
 """
 import argparse
 import ctypes as C
@@ -45,15 +46,17 @@ def main():
     ap.add_argument("--mh", type=int, default=0, help="textmark / watermark: mask or watermark height (0 = mw / 5)")
     ap.add_argument("--margin", type=int, default=-1, help="textmark: margin (-1 = the mask width, bimg's default)")
     ap.add_argument("--opacity", type=float, default=0.25)
-    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444 / jpegd* : JPEG quality")
-    ap.add_argument("--shrink", type=int, default=2, choices=[1, 2, 4, 8],
-                    help="jpegds420 / jpegds444: decode the w x h file's coefficients at 1/shrink")
+    ap.add_argument("--q", type=int, default=75, help="jpegc420 / jpegc444 / jpegd* / jpegrt* : JPEG quality")
+    ap.add_argument("--shrink", type=int, default=0, choices=[0, 1, 2, 4, 8],
+                    help="jpegds420 / jpegds444: decode the w x h file's coefficients at 1/shrink (0 = 2); "
+                         "jpegrt420 / jpegrt444: the round trip's decode at 1/shrink (0 = 1)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
     ap.add_argument("--sampling", choices=["corner", "centre"], default=None,
                     help="reduce sampling convention (mipx_set_reduce_sampling); default: the library's")
     a = ap.parse_args()
+    a.shrink = a.shrink or (1 if a.op.startswith("jpegrt") else 2)
     dev = torch.device("cuda", 0)
     check(lib.mipx_set_device(0))
     if a.sampling:
@@ -106,6 +109,11 @@ def main():
         if a.op.startswith("jpegds"):   # ... at 1/shrink: the same payload, RGB at the decoded size
             ow, oh = -(-w // a.shrink), -(-h // a.shrink)
             out_img = ow * oh * 3
+    if a.op in ("jpegrt420", "jpegrt444"):   # RGB in, RGB out at 1/shrink; the planes in between are not credited
+        b = ob = 3
+        layout = 1 if a.op == "jpegrt420" else 0
+        ow, oh = -(-w // a.shrink), -(-h // a.shrink)
+        in_img, out_img = w * h * 3, ow * oh * 3
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
@@ -169,6 +177,8 @@ def main():
             return lib.mipx_op_jpegd_to_rgb(X, Y, n, w, h, layout, WS, WSB, sp)
         if a.op in ("jpegds420", "jpegds444"):
             return lib.mipx_op_jpegd_to_rgb_scaled(X, Y, n, w, h, layout, a.shrink, WS, WSB, sp)
+        if a.op in ("jpegrt420", "jpegrt444"):
+            return lib.mipx_op_jpeg_roundtrip(X, Y, n, w, h, layout, a.q, a.shrink, WS, WSB, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -199,7 +209,7 @@ def main():
     alg = n * (in_img + out_img)   # bytes = input + output
     line = {"op": a.op, "w": w, "h": h, "b": b, "n": n, "s": a.s, "s2": s2, "out": [ow, oh, ob],
             "sampling": ["corner", "centre"][lib.mipx_reduce_sampling()]}
-    if a.op.startswith("jpegds"):
+    if a.op.startswith(("jpegds", "jpegrt")):
         line["shrink"] = a.shrink
     if not a.ab:
         ms = measure()
