@@ -13,6 +13,7 @@ from .engine import (DeviceBuffer, Engine, GuardedBuffer, device_count, execute,
                      smartcrop_origins, synchronize, plan_set_ycc_input, ycc_bytes, ycc_to_rgb, YCC_444, YCC_420,
                      plan_set_jpegc_output, jpegc_bytes, jpeg_qtables, rgb_to_jpegc,
                      plan_set_jpegd_input, plan_set_jpegd_input_scaled, jpegd_bytes, jpegd_to_rgb,
-                     jpegd_to_rgb_scaled, plan_add_jpeg_roundtrip, jpeg_roundtrip)
+                     jpegd_to_rgb_scaled, plan_add_jpeg_roundtrip, jpeg_roundtrip,
+                     plan_set_jpeg_scan_output, jpeg_scan_bytes, rgb_to_jpeg_scan, jpegc_to_scan, scan_slot)
 
 __version__ = "0.2.0"

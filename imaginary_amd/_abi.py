@@ -30,12 +30,14 @@ TYPES = {"unknown": 0, "jpeg": 1, "webp": 2, "png": 3, "tiff": 4, "gif": 5, "pdf
          "magick": 8, "heif": 9, "avif": 10}
 
 (OP_ROT, OP_FLIP, OP_SHRINK, OP_REDUCE, OP_EXTRACT, OP_EMBED, OP_SMARTCROP, OP_BLUR, OP_WATERMARK,
- OP_AFFINE, OP_ZOOM, OP_FLATTEN, OP_BW, OP_TEXTMARK, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT) = range(1, 19)
+ OP_AFFINE, OP_ZOOM, OP_FLATTEN, OP_BW, OP_TEXTMARK, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE) = range(1, 20)
 OP_NAMES = {OP_ROT: "rot", OP_FLIP: "flip", OP_SHRINK: "shrink", OP_REDUCE: "reduce",
             OP_EXTRACT: "extract", OP_EMBED: "embed", OP_SMARTCROP: "smartcrop",
             OP_BLUR: "blur", OP_WATERMARK: "watermark", OP_AFFINE: "affine", OP_ZOOM: "zoom",
             OP_FLATTEN: "flatten", OP_BW: "bw", OP_TEXTMARK: "textmark", OP_YCC: "ycc", OP_JPEGC: "jpegc",
-            OP_JPEGD: "jpegd", OP_JPEGRT: "jpegrt"}
+            OP_JPEGD: "jpegd", OP_JPEGRT: "jpegrt", OP_JPEGE: "jpege"}
+JPEG_SCAN_HEADER_BYTES = 16   # MIPX_JPEG_SCAN_HEADER_BYTES: length, status, bits, 0 as little-endian uint32
+JPEG_SCAN_OK, JPEG_SCAN_OVERFLOW, JPEG_SCAN_UNCODABLE = 0, 1, 2   # MIPX_JPEG_SCAN_*
 YCC_444 = 0   # planar JPEG input, coefficient input and output (MIPX_YCC_*): Cb, Cr at full size ...
 YCC_420 = 1   # ... or at ceil(w / 2) x ceil(h / 2)
 INTERPRETATION_SRGB = 22
@@ -136,6 +138,8 @@ _SIG = {
     "mipx_plan_set_ycc_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
     "mipx_jpegc_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegc_output": (C.c_int, [C.POINTER(MipxPlan), _I, _I]),
+    "mipx_jpeg_scan_bytes": (C.c_size_t, [_I, _I, _I]),
+    "mipx_plan_set_jpeg_scan_output": (C.c_int, [C.POINTER(MipxPlan), _I, _I]),
     "mipx_jpeg_qtables": (C.c_int, [_I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "mipx_jpegd_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegd_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
@@ -161,6 +165,8 @@ _SIG = {
     "mipx_op_text_watermark": (C.c_int, [_U8P, _U8P, _U8P, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.POINTER(_I), _P]),
     "mipx_op_ycc_to_rgb": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P]),
     "mipx_op_rgb_to_jpegc": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P]),
+    "mipx_op_jpegc_to_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, _P]),
+    "mipx_op_rgb_to_jpeg_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P]),
     "mipx_op_jpegd_to_rgb": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_jpegd_to_rgb_scaled": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_jpeg_roundtrip": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),

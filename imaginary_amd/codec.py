@@ -247,13 +247,9 @@ def _jpegc_geometry(w: int, h: int, layout: int):
     return [(ywb, yhb, 2), (cwb, chb, 1), (cwb, chb, 1)], cwb, chb
 
 
-def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes:
-    """A baseline JFIF file from the engine's quantised coefficients (MIPX_OP_JPEGC: int16,
-    Y then Cb then Cr, real blocks in raster order, natural order inside a block), made at
-    `quality` in `layout` (YCC_444 / YCC_420).  Stand-in for libjpeg's jpeg_write_coefficients:
-    the Annex K Huffman tables, one interleaved scan, and libjpeg's dummy blocks where the
-    real blocks do not fill whole MCUs (zero AC; DC copied from the block to the left, or,
-    in a wholly dummy block row, from the last block of the same MCU's row above)."""
+def _padded_planes(coefs, w: int, h: int, layout: int):
+    """The coefficients per component as (rows, columns, 64) int32 in zigzag order, padded to
+    whole MCUs with libjpeg's dummy blocks; also the components and the MCU grid."""
     comps, mw, mh = _jpegc_geometry(w, h, layout)
     c = np.ascontiguousarray(coefs).view(np.int16).ravel() if np.asarray(coefs).dtype == np.uint8 \
         else np.asarray(coefs, dtype=np.int16).ravel()
@@ -270,6 +266,13 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes
             for m in range(mw):
                 full[y, m * s:(m + 1) * s, 0] = full[y - 1, m * s + s - 1, 0]
         planes.append(full[:, :, list(ZIGZAG)].astype(np.int32))
+    return planes, comps, mw, mh
+
+
+def jpeg_header(w: int, h: int, layout: int, quality: int) -> bytes:
+    """SOI through SOS of the baseline JFIF file encode_jpeg_coefs writes: it depends on the
+    size, the sampling (YCC_444 / YCC_420) and the quality only, not on the image."""
+    comps, _, _ = _jpegc_geometry(w, h, layout)
     lum, chrom = jpeg_qtables(quality)
 
     def seg(marker, body):
@@ -286,17 +289,24 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes
     for tc in (0x00, 0x10, 0x01, 0x11):
         out += seg(0xC4, bytes([tc]) + HUFFMAN_TABLES[tc][0] + HUFFMAN_TABLES[tc][1])
     out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    return bytes(out)
 
+
+def jpeg_scan_bits(coefs, w: int, h: int, layout: int):
+    """(scan, bits): jpeg_scan's bytes, and the scan's length in bits before the last byte is
+    padded and the 0xFF bytes are stuffed (what the engine's slot header reports)."""
+    planes, comps, mw, mh = _padded_planes(coefs, w, h, layout)
     dc_codes = [_huff_codes(_HUFF_DC_LUM), _huff_codes(_HUFF_DC_CHR)]
     ac_codes = [_huff_codes(_HUFF_AC_LUM), _huff_codes(_HUFF_AC_CHR)]
-    acc, nbits = 0, 0            # the bit buffer, as one growing integer per MCU row
+    acc, nbits, total = 0, 0, 0  # the bit buffer, as one growing integer per MCU row
     scan = bytearray()
     pred = [0, 0, 0]
 
     def put(code, length):
-        nonlocal acc, nbits
+        nonlocal acc, nbits, total
         acc = (acc << length) | code
         nbits += length
+        total += length
 
     def put_value(v, size):      # the `size` low bits of v, or of v - 1 when negative
         put((v if v >= 0 else v - 1) & ((1 << size) - 1), size)
@@ -324,6 +334,8 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes
                         d = int(blk[0]) - pred[ci]
                         pred[ci] = int(blk[0])
                         size = abs(d).bit_length()
+                        if size > 11:
+                            raise ValueError(f"DC difference {d}: no Annex K code past 2047")
                         put(*dc_codes[t][size])
                         if size:
                             put_value(d, size)
@@ -337,6 +349,8 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes
                                 run -= 16
                             v = int(blk[k])
                             size = abs(v).bit_length()
+                            if size > 10:
+                                raise ValueError(f"AC coefficient {v}: no Annex K code past 1023")
                             put(*ac_codes[t][(run << 4) | size])
                             put_value(v, size)
                             prev = k
@@ -344,9 +358,31 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes
                             put(*ac_codes[t][0x00])
         flush()
     flush(final=True)
-    out += scan
-    out += b"\xff\xd9"
-    return bytes(out)
+    return bytes(scan), total
+
+
+def jpeg_scan(coefs, w: int, h: int, layout: int) -> bytes:
+    """The entropy-coded scan of the engine's quantised coefficients (MIPX_OP_JPEGC: int16, Y
+    then Cb then Cr, real blocks in raster order, natural order inside a block), without EOI:
+    the Annex K Huffman tables, one interleaved scan, libjpeg's dummy blocks where the real
+    blocks do not fill whole MCUs (zero AC; DC copied from the block to the left, or, in a
+    wholly dummy block row, from the last block of the same MCU's row above), the last byte
+    padded with 1-bits, every 0xFF followed by 0x00.  What a plan that ends with MIPX_OP_JPEGE
+    gives (PARITY_ASSUMPTIONS.md row 21).  ValueError for a coefficient no Annex K code exists
+    for: an AC magnitude above 1023 or a DC difference magnitude above 2047."""
+    return jpeg_scan_bits(coefs, w, h, layout)[0]
+
+
+def jpeg_from_scan(scan, w: int, h: int, layout: int, quality: int) -> bytes:
+    """The file: jpeg_header, the scan (jpeg_scan, or the bytes of an engine slot), EOI."""
+    return jpeg_header(w, h, layout, quality) + bytes(scan) + b"\xff\xd9"
+
+
+def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes:
+    """A baseline JFIF file from the engine's quantised coefficients (MIPX_OP_JPEGC), made at
+    `quality` in `layout` (YCC_444 / YCC_420).  Stand-in for libjpeg's jpeg_write_coefficients:
+    jpeg_from_scan of jpeg_scan."""
+    return jpeg_from_scan(jpeg_scan(coefs, w, h, layout), w, h, layout, quality)
 
 
 # ---- quantised coefficients from a JPEG (the engine's MIPX_OP_JPEGD input) -----------------

@@ -1,0 +1,451 @@
+// k_jpege.hip — a JPEG encoder's back half on gfx950 (PARITY_ASSUMPTIONS.md row 21): the quantised
+// coefficients k_jpegc.hip writes in, the finished entropy-coded scan out, one slot per image
+// (include/mipx.h, MIPX_OP_JPEGE): baseline Huffman coding with the Annex K.3 tables, one
+// interleaved scan, libjpeg's dummy blocks, 1-padding, 0xFF stuffing.  Integer only; the output
+// does not depend on the order workgroups run in.
+//
+// A block's bits depend on the block and on the DC of the block before it in scan order, and
+// both are in memory, so nothing is serial but two prefix sums: of the blocks' bit counts (where a
+// block starts) and of the 0xFF bytes (where a byte lands after stuffing).  Every dependency
+// between workgroups is a launch boundary on the stream; no kernel waits for another workgroup.
+//   memset           the per-image records and the unstuffed streams (the pack kernel ORs into them)
+//   k_jpege_count    one lane per block of the scan, dummy blocks included, kJpegeTile blocks per
+//                    workgroup: its bit count, the tile's sum, a flag for a value without a code
+//   k_jpege_scan<0>  one workgroup per image over the tile sums (a few hundred): where each tile
+//                    starts, the scan's bits, and the verdict: uncodable, or too long for the slot
+//   k_jpege_pack     the same lanes code their blocks again, now at their bit offset, into the
+//                    unstuffed stream: whole words by plain stores, a block's first and last
+//                    word by a 32-bit atomic OR (order-independent); the last block pads with 1s
+//   k_jpege_ffcount  0xFF bytes per kJpegeChunk bytes of stream
+//   k_jpege_scan<1>  one workgroup per image over those counts: the final length, overflow again
+//   k_jpege_stuff    bytes to the slot with the 0x00s inserted, every store checked against the
+//                    capacity; the header
+// Images whose verdict is not "ok" are skipped by every later kernel but for the header.
+//
+// The count and pack kernels stage their tile's blocks through LDS with coalesced 16-byte loads
+// (8 lanes per block), blocks 33 dwords apart, so that the lanes of a wave, each walking its own
+// block in zigzag order, read 32 different banks.  Scan order is not memory order (4:2:0
+// interleaves two Y block rows and both chroma planes), but every block is one whole 128-byte line.
+// Coefficients and slots start on any byte: global accesses to them are plain unaligned ones.
+#include <hip/hip_runtime.h>
+
+#include "device_common.h"
+
+namespace mipx {
+namespace {
+
+using namespace dev;
+
+constexpr uint32_t kTile = kJpegeTile;    // threads of every kernel here, and blocks per tile
+constexpr uint32_t kChunk = kJpegeChunk;  // stream bytes per workgroup: a dword per lane
+constexpr uint32_t kPitch = 33;           // dwords between two blocks in LDS
+constexpr uint32_t kNone = 0xffffffffu;
+static_assert(kChunk == 4 * kTile, "a dword of stream per lane");
+
+struct JpegeInfo {  // per image, zeroed every call
+    unsigned long long bits;  // the scan before padding and stuffing
+    uint32_t ff;              // its 0xFF bytes
+    uint32_t status;          // MIPX_JPEG_SCAN_*
+    uint32_t flags;           // 1: a coefficient without a code
+    uint32_t pad[3];
+};
+static_assert(sizeof(JpegeInfo) == 32, "JpegeWork sizes the records");
+
+struct JpegeArgs {
+    const u8 *coefs;  // cap bytes per image
+    u8 *out;          // 16 + cap bytes per image
+    const uint32_t *codes;  // build_jpege_codes
+    JpegeInfo *info;
+    uint32_t *stream;  // cap bytes per image
+    uint32_t *counts;
+    uint32_t *tile_sums;
+    unsigned long long *tile_offs;
+    uint32_t *chunk_sums;
+    unsigned long long *chunk_offs;
+    uint32_t cap;             // bytes of one image's coefficients = the capacity of its scan
+    uint32_t ywb, yhb;        // real Y blocks across and down
+    uint32_t mw;              // MCUs across
+    uint32_t cb_off, cr_off;  // byte offsets of the Cb and Cr coefficients
+    uint32_t blocks, tiles, chunks;  // per image: blocks of the scan, tiles of them, chunks of the stream
+};
+
+__constant__ uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// Exclusive prefix of v over the workgroup's 256 lanes; *total = the sum.  wsum: 4 words of LDS.
+__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *wsum, uint32_t *total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d);
+        if (lane >= static_cast<uint32_t>(d)) inc += t;
+    }
+    if (lane == 63u) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kTile / 64u; ++i) {
+        const uint32_t s = wsum[i];
+        base += i < wave ? s : 0u;
+        tot += s;
+    }
+    __syncthreads();  // wsum is free again
+    *total = tot;
+    return base + inc - v;
+}
+
+__device__ __forceinline__ int load_i16(const u8 *p) {
+    int16_t v;
+    __builtin_memcpy(&v, p, 2);
+    return v;
+}
+
+// Block s of the scan: the byte offset of the block its DC comes from (itself, or for a dummy block
+// the real block libjpeg copies it from), whether it is real, which tables code it, and the block
+// before it of the same component (kNone: the component's first, predicted from 0).
+template <int LAYOUT>
+__device__ __forceinline__ uint32_t block_src(const JpegeArgs &a, uint32_t s, bool *real, uint32_t *chroma,
+                                              uint32_t *prev) {
+    if (LAYOUT == MIPX_YCC_444) {  // Y Cb Cr per MCU; MCUs are the blocks in raster order
+        const uint32_t m = s / 3u, c = s - 3u * m;
+        *real = true, *chroma = c ? 1u : 0u;
+        *prev = m ? s - 3u : kNone;
+        return (c == 0u ? 0u : c == 1u ? a.cb_off : a.cr_off) + m * 128u;
+    }
+    const uint32_t m = s / 6u, j = s - 6u * m;  // Y00 Y01 Y10 Y11 Cb Cr
+    if (j >= 4u) {
+        *real = true, *chroma = 1u;
+        *prev = m ? s - 6u : kNone;
+        return (j == 4u ? a.cb_off : a.cr_off) + m * 128u;
+    }
+    *chroma = 0u;
+    *prev = j ? s - 1u : (m ? s - 3u : kNone);
+    const uint32_t my = m / a.mw, mx = m - my * a.mw;
+    uint32_t by = 2u * my + (j >> 1), bx = 2u * mx + (j & 1u);
+    *real = by < a.yhb && bx < a.ywb;
+    if (by >= a.yhb) by -= 1u, bx = 2u * mx + 1u;  // a dummy row: the last block of the MCU's row above
+    if (bx >= a.ywb) bx = a.ywb - 1u;               // a dummy column: the block to the left
+    return (by * a.ywb + bx) * 128u;
+}
+
+// What a lane knows of its block once the tile is staged.
+struct Lane {
+    bool real;  // its coefficients are staged; a dummy block has only the DC
+    int dc, pred;
+    uint32_t chroma;
+    bool valid;  // a block of the scan (the last tile has lanes past it)
+};
+
+// Stages the tile's real blocks into `blk` and describes the lane's own one.  Ends with a barrier.
+template <int LAYOUT>
+__device__ __forceinline__ Lane stage_tile(const JpegeArgs &a, const u8 *coefs, uint32_t tile, uint32_t *blk,
+                                           uint32_t *src) {
+    const uint32_t tid = threadIdx.x, s = tile * kTile + tid;
+    Lane me;
+    me.valid = s < a.blocks;
+    me.real = false, me.dc = 0, me.pred = 0, me.chroma = 0;
+    uint32_t mine = kNone;
+    if (me.valid) {
+        bool preal;
+        uint32_t prev, pchroma, pprev;
+        const uint32_t off = block_src<LAYOUT>(a, s, &me.real, &me.chroma, &prev);
+        me.dc = load_i16(coefs + off);
+        if (prev != kNone) me.pred = load_i16(coefs + block_src<LAYOUT>(a, prev, &preal, &pchroma, &pprev));
+        if (me.real) mine = off;
+    }
+    src[tid] = mine;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; ++i) {  // 8 lanes load a block's 128 bytes
+        const uint32_t t = tid + kTile * i, b = t >> 3, part = t & 7u;
+        const uint32_t off = src[b];
+        if (off == kNone) continue;
+        uint4 v;
+        __builtin_memcpy(&v, coefs + off + part * 16u, 16);  // any alignment: one global_load_dwordx4
+        uint32_t *d = blk + b * kPitch + part * 4u;
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+    }
+    __syncthreads();
+    return me;
+}
+
+__device__ __forceinline__ uint32_t bit_length(uint32_t v) { return v ? 32u - __builtin_clz(v) : 0u; }
+
+// Codes one block (coef: its staged coefficients, natural order) into `sink` (put(bits, count),
+// count <= 27); true when a value had no code.  Such a value is coded as the largest category, so
+// that counting and packing still agree.
+template <class Sink>
+__device__ __forceinline__ bool code_block(const Lane &me, const int16_t *coef, const uint32_t *codes, Sink &sink) {
+    bool bad = false;
+    const uint32_t *dc_codes = codes + me.chroma * 2u * kJpegeCodesPerTable, *ac_codes = dc_codes + kJpegeCodesPerTable;
+    {
+        const int d = me.dc - me.pred;
+        uint32_t size = bit_length(static_cast<uint32_t>(d < 0 ? -d : d));
+        if (size > 11u) bad = true, size = 11u;
+        const uint32_t e = dc_codes[size];
+        const uint32_t low = static_cast<uint32_t>(d < 0 ? d - 1 : d) & ((1u << size) - 1u);
+        sink.put((e & 0xffffu) << size | low, (e >> 16) + size);
+    }
+    uint32_t run = 0;
+    if (me.real) {
+        const uint32_t zrl = ac_codes[0xf0];
+        for (uint32_t k0 = 1; k0 < 64u; k0 += 7u) {  // 9 groups of 7: the group's LDS reads go out together
+            int group[7];
+#pragma unroll
+            for (uint32_t j = 0; j < 7u; ++j) group[j] = coef[kZigzag[k0 + j]];
+#pragma unroll
+            for (uint32_t j = 0; j < 7u; ++j) {
+                const int v = group[j];
+                if (v == 0) {
+                    ++run;
+                    continue;
+                }
+                for (; run > 15u; run -= 16u) sink.put(zrl & 0xffffu, zrl >> 16);
+                uint32_t size = bit_length(static_cast<uint32_t>(v < 0 ? -v : v));
+                if (size > 10u) bad = true, size = 10u;
+                const uint32_t e = ac_codes[run << 4 | size];
+                const uint32_t low = static_cast<uint32_t>(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
+                sink.put((e & 0xffffu) << size | low, (e >> 16) + size);
+                run = 0;
+            }
+        }
+    } else {
+        run = 63;
+    }
+    if (run) sink.put(ac_codes[0] & 0xffffu, ac_codes[0] >> 16);  // EOB, unless coefficient 63 is coded
+    return bad;
+}
+
+struct CountSink {
+    uint32_t bits = 0;
+    __device__ __forceinline__ void put(uint32_t, uint32_t count) { bits += count; }
+};
+
+// Bits into the image's unstuffed stream from bit `at` on, most significant first.  The stream is
+// bytes; a word holds 4 of them little-endian, so a word of 32 stream bits is stored byte-swapped.
+struct PackSink {
+    uint32_t *words;
+    uint32_t limit;  // words of the stream
+    uint32_t wi, fill;
+    unsigned long long acc;
+    bool first = true;
+    __device__ __forceinline__ PackSink(uint32_t *w, uint32_t lim, unsigned long long at)
+        : words(w), limit(lim), wi(static_cast<uint32_t>(at >> 5)), fill(static_cast<uint32_t>(at) & 31u), acc(0) {}
+    __device__ __forceinline__ void put(uint32_t v, uint32_t count) {
+        acc = acc << count | v;
+        fill += count;
+        if (fill >= 32u) {
+            fill -= 32u;
+            const uint32_t w = __builtin_bswap32(static_cast<uint32_t>(acc >> fill));
+            acc &= (1ull << fill) - 1ull;
+            if (wi < limit) {
+                if (first) atomicOr(words + wi, w);  // shared with the block before
+                else words[wi] = w;                  // all 32 bits are this block's
+            }
+            first = false;
+            ++wi;
+        }
+    }
+    __device__ __forceinline__ void finish() {  // the last, partial word: shared with the block after
+        if (fill && wi < limit) atomicOr(words + wi, __builtin_bswap32(static_cast<uint32_t>(acc << (32u - fill))));
+    }
+};
+
+__device__ __forceinline__ void load_codes(const JpegeArgs &a, uint32_t *codes) {
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) codes[threadIdx.x + kTile * i] = a.codes[threadIdx.x + kTile * i];
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(kTile) k_jpege_count(const JpegeArgs a) {
+    __shared__ uint32_t blk[kTile * kPitch];
+    __shared__ uint32_t codes[4 * kJpegeCodesPerTable];
+    __shared__ uint32_t src[kTile];
+    __shared__ uint32_t wsum[kTile / 64];
+    const uint32_t img = blockIdx.y, tile = blockIdx.x;
+    load_codes(a, codes);
+    const Lane me = stage_tile<LAYOUT>(a, a.coefs + static_cast<size_t>(img) * a.cap, tile, blk, src);
+    CountSink sink;
+    bool bad = false;
+    if (me.valid) {
+        bad = code_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), codes, sink);
+        a.counts[static_cast<size_t>(img) * a.blocks + tile * kTile + threadIdx.x] = sink.bits;
+    }
+    uint32_t total;
+    block_scan(sink.bits, wsum, &total);
+    if (threadIdx.x == 0) a.tile_sums[static_cast<size_t>(img) * a.tiles + tile] = total;
+    if (bad) atomicOr(&a.info[img].flags, 1u);
+}
+
+// One workgroup per image: the exclusive scan of its per-tile (STAGE 0) or per-chunk (STAGE 1)
+// sums, and what follows from the total.
+template <int STAGE>
+__global__ void __launch_bounds__(kTile) k_jpege_scan(const JpegeArgs a) {
+    __shared__ uint32_t wsum[kTile / 64];
+    const uint32_t img = blockIdx.x, tid = threadIdx.x;
+    JpegeInfo *info = a.info + img;
+    uint32_t count = a.tiles;
+    const uint32_t *sums = a.tile_sums + static_cast<size_t>(img) * a.tiles;
+    unsigned long long *offs = a.tile_offs + static_cast<size_t>(img) * a.tiles;
+    unsigned long long bytes = 0;
+    if (STAGE == 1) {
+        if (info->status != MIPX_JPEG_SCAN_OK) return;
+        bytes = (info->bits + 7ull) >> 3;  // <= cap
+        count = static_cast<uint32_t>((bytes + kChunk - 1ull) / kChunk);  // the chunks k_jpege_ffcount wrote
+        sums = a.chunk_sums + static_cast<size_t>(img) * a.chunks;
+        offs = a.chunk_offs + static_cast<size_t>(img) * a.chunks;
+    }
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < count; base += kTile) {
+        const uint32_t i = base + tid;
+        uint32_t total;
+        const uint32_t before = block_scan(i < count ? sums[i] : 0u, wsum, &total);
+        if (i < count) offs[i] = carry + before;
+        carry += total;
+    }
+    if (tid != 0) return;
+    if (STAGE == 0) {
+        info->bits = carry;
+        info->status = info->flags ? MIPX_JPEG_SCAN_UNCODABLE
+                                   : ((carry + 7ull) >> 3) > a.cap ? MIPX_JPEG_SCAN_OVERFLOW : MIPX_JPEG_SCAN_OK;
+    } else {
+        info->ff = static_cast<uint32_t>(carry);
+        if (bytes + carry > a.cap) info->status = MIPX_JPEG_SCAN_OVERFLOW;
+    }
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(kTile) k_jpege_pack(const JpegeArgs a) {
+    __shared__ uint32_t blk[kTile * kPitch];
+    __shared__ uint32_t codes[4 * kJpegeCodesPerTable];
+    __shared__ uint32_t src[kTile];
+    __shared__ uint32_t wsum[kTile / 64];
+    const uint32_t img = blockIdx.y, tile = blockIdx.x, s = tile * kTile + threadIdx.x;
+    if (a.info[img].status != MIPX_JPEG_SCAN_OK) return;  // the whole workgroup
+    load_codes(a, codes);
+    const Lane me = stage_tile<LAYOUT>(a, a.coefs + static_cast<size_t>(img) * a.cap, tile, blk, src);
+    uint32_t total;
+    const uint32_t before = block_scan(me.valid ? a.counts[static_cast<size_t>(img) * a.blocks + s] : 0u, wsum, &total);
+    if (!me.valid) return;
+    const unsigned long long at = a.tile_offs[static_cast<size_t>(img) * a.tiles + tile] + before;
+    PackSink sink(a.stream + static_cast<size_t>(img) * (a.cap / 4u), a.cap / 4u, at);
+    code_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), codes, sink);
+    if (s + 1u == a.blocks) {  // the scan's last block: 1-bits up to the byte
+        const uint32_t pad = (8u - (static_cast<uint32_t>(a.info[img].bits) & 7u)) & 7u;
+        if (pad) sink.put((1u << pad) - 1u, pad);
+    }
+    sink.finish();
+}
+
+__device__ __forceinline__ uint32_t ff_bytes(uint32_t word, unsigned long long first, unsigned long long bytes) {
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) c += (first + j < bytes && ((word >> (8u * j)) & 0xffu) == 0xffu) ? 1u : 0u;
+    return c;
+}
+
+__global__ void __launch_bounds__(kTile) k_jpege_ffcount(const JpegeArgs a) {
+    __shared__ uint32_t wsum[kTile / 64];
+    const uint32_t img = blockIdx.y, chunk = blockIdx.x;
+    const JpegeInfo *info = a.info + img;
+    if (info->status != MIPX_JPEG_SCAN_OK) return;
+    const unsigned long long bytes = (info->bits + 7ull) >> 3;
+    const unsigned long long first = static_cast<unsigned long long>(chunk) * kChunk + threadIdx.x * 4u;
+    if (static_cast<unsigned long long>(chunk) * kChunk >= bytes) return;
+    const uint32_t word = first < a.cap ? a.stream[static_cast<size_t>(img) * (a.cap / 4u) + first / 4u] : 0u;
+    uint32_t total;
+    block_scan(ff_bytes(word, first, bytes), wsum, &total);
+    if (threadIdx.x == 0) a.chunk_sums[static_cast<size_t>(img) * a.chunks + chunk] = total;
+}
+
+__global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
+    __shared__ uint32_t wsum[kTile / 64];
+    const uint32_t img = blockIdx.y, chunk = blockIdx.x;
+    const JpegeInfo *info = a.info + img;
+    u8 *slot = a.out + static_cast<size_t>(img) * (MIPX_JPEG_SCAN_HEADER_BYTES + static_cast<size_t>(a.cap));
+    const uint32_t status = info->status;
+    const unsigned long long bits = info->bits, bytes = (bits + 7ull) >> 3;
+    if (chunk == 0 && threadIdx.x == 0) {
+        const unsigned long long length = status == MIPX_JPEG_SCAN_OK         ? bytes + info->ff
+                                          : status == MIPX_JPEG_SCAN_OVERFLOW ? bytes
+                                                                              : 0ull;
+        uint4 hdr;
+        hdr.x = length > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(length);
+        hdr.y = status;
+        hdr.z = bits > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(bits);
+        hdr.w = 0u;
+        __builtin_memcpy(slot, &hdr, 16);  // any alignment: one global_store_dwordx4
+    }
+    if (status != MIPX_JPEG_SCAN_OK || static_cast<unsigned long long>(chunk) * kChunk >= bytes) return;
+    const unsigned long long first = static_cast<unsigned long long>(chunk) * kChunk + threadIdx.x * 4u;
+    const uint32_t word = first < a.cap ? a.stream[static_cast<size_t>(img) * (a.cap / 4u) + first / 4u] : 0u;
+    uint32_t total;
+    const uint32_t before = block_scan(ff_bytes(word, first, bytes), wsum, &total);
+    unsigned long long pos = first + a.chunk_offs[static_cast<size_t>(img) * a.chunks + chunk] + before;
+    u8 *data = slot + MIPX_JPEG_SCAN_HEADER_BYTES;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        if (first + j >= bytes) break;
+        const uint32_t b = (word >> (8u * j)) & 0xffu;
+        if (pos < a.cap) data[pos] = static_cast<u8>(b);
+        ++pos;
+        if (b == 0xffu) {
+            if (pos < a.cap) data[pos] = 0;
+            ++pos;
+        }
+    }
+}
+
+}  // namespace
+
+int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, u8 *work, hipStream_t st) {
+    const JpegeWork W(n, w, h);
+    const bool sub = layout == MIPX_YCC_420;
+    JpegeArgs a;
+    a.coefs = d_coefs, a.out = d_out;
+    a.codes = device_jpege_codes();
+    if (!a.codes) {
+        set_error("jpeg coefficients to scan: no Huffman code table on the device");
+        return MIPX_EDEVICE;
+    }
+    a.info = reinterpret_cast<JpegeInfo *>(work + W.info);
+    a.stream = reinterpret_cast<uint32_t *>(work + W.stream);
+    a.counts = reinterpret_cast<uint32_t *>(work + W.counts);
+    a.tile_sums = reinterpret_cast<uint32_t *>(work + W.tile_sums);
+    a.tile_offs = reinterpret_cast<unsigned long long *>(work + W.tile_offs);
+    a.chunk_sums = reinterpret_cast<uint32_t *>(work + W.chunk_sums);
+    a.chunk_offs = reinterpret_cast<unsigned long long *>(work + W.chunk_offs);
+    a.cap = static_cast<uint32_t>(mipx_jpegc_bytes(w, h, layout));
+    a.ywb = (static_cast<uint32_t>(w) + 7u) / 8u, a.yhb = (static_cast<uint32_t>(h) + 7u) / 8u;
+    const uint32_t cwb = sub ? ((static_cast<uint32_t>(w) + 1u) / 2u + 7u) / 8u : a.ywb;
+    const uint32_t chb = sub ? ((static_cast<uint32_t>(h) + 1u) / 2u + 7u) / 8u : a.yhb;
+    a.mw = cwb;
+    a.cb_off = a.ywb * a.yhb * 128u;
+    a.cr_off = a.cb_off + cwb * chb * 128u;
+    const unsigned long long blocks = static_cast<unsigned long long>(cwb) * chb * (sub ? 6u : 3u);
+    a.blocks = static_cast<uint32_t>(blocks);
+    a.tiles = static_cast<uint32_t>((blocks + kTile - 1) / kTile);
+    a.chunks = (a.cap + kChunk - 1u) / kChunk;
+    if (a.cap > W.cap || blocks > W.blocks || !grid_ok(a.tiles) || !grid_ok(a.chunks)) return MIPX_EUNSUPPORTED;
+    MIPX_HIP(hipMemsetAsync(work + W.info, 0, (W.stream - W.info) + static_cast<size_t>(n) * a.cap, st));
+    const dim3 threads(kTile), by_tile(a.tiles, n), by_chunk(a.chunks, n), by_image(n);
+    int e;
+    if (sub) hipLaunchKernelGGL(k_jpege_count<MIPX_YCC_420>, by_tile, threads, 0, st, a);
+    else hipLaunchKernelGGL(k_jpege_count<MIPX_YCC_444>, by_tile, threads, 0, st, a);
+    if ((e = launch_check("k_jpege_count"))) return e;
+    hipLaunchKernelGGL(k_jpege_scan<0>, by_image, threads, 0, st, a);
+    if ((e = launch_check("k_jpege_scan<0>"))) return e;
+    if (sub) hipLaunchKernelGGL(k_jpege_pack<MIPX_YCC_420>, by_tile, threads, 0, st, a);
+    else hipLaunchKernelGGL(k_jpege_pack<MIPX_YCC_444>, by_tile, threads, 0, st, a);
+    if ((e = launch_check("k_jpege_pack"))) return e;
+    hipLaunchKernelGGL(k_jpege_ffcount, by_chunk, threads, 0, st, a);
+    if ((e = launch_check("k_jpege_ffcount"))) return e;
+    hipLaunchKernelGGL(k_jpege_scan<1>, by_image, threads, 0, st, a);
+    if ((e = launch_check("k_jpege_scan<1>"))) return e;
+    hipLaunchKernelGGL(k_jpege_stuff, by_chunk, threads, 0, st, a);
+    return launch_check("k_jpege_stuff");
+}
+
+}  // namespace mipx

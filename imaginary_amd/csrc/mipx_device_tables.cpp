@@ -20,7 +20,7 @@ namespace mipx {
 namespace {
 
 enum Kind {
-    kReduce, kPairs, kI8, kI8s, kI8sFold, kVPlan, kHops, kBlurOps, kGauss, kColour, kBicubic, kBlob, kEnlmAxis, kJpegc, kKinds
+    kReduce, kPairs, kI8, kI8s, kI8sFold, kVPlan, kHops, kBlurOps, kGauss, kColour, kBicubic, kBlob, kEnlmAxis, kJpegc, kJpegeCodes, kKinds
 };
 
 // The parameters a table was built from.  Fixed-size kinds leave `contents` empty (no heap
@@ -199,6 +199,8 @@ const int *device_bicubic_table() { return as<int>(fetch(key_of(kBicubic), build
 const uint32_t *device_jpegc_recips(int quality) {
     return as<uint32_t>(fetch(key_of(kJpegc, 0, quality), [&] { return build_jpegc_recips(quality); }));
 }
+
+const uint32_t *device_jpege_codes() { return as<uint32_t>(fetch(key_of(kJpegeCodes), build_jpege_codes)); }
 
 // Small host-built constant tables (per-lane MFMA operands and the like) copied to the
 // current device once, keyed by their contents.

@@ -99,6 +99,7 @@ const signed char *device_blur_ops(const std::vector<int> &mask, int bands, int 
 const float *device_colour_tables();  // [256 v2y | kQuantElements cbrt | 257 y2v]
 const int *device_bicubic_table();     // 129 x 4
 const uint32_t *device_jpegc_recips(int quality);  // k_jpegc: [lum 64 | chr 64] reciprocals of the quality's tables
+const uint32_t *device_jpege_codes();               // k_jpege: the four Annex K Huffman tables (build_jpege_codes)
 // float copy of the integer gaussmat mask; *scale = mask sum
 const float *device_gauss_table(double sigma, double min_ampl, int *n_taps, int *scale);
 // `bytes` of host data on the current device, cached by contents (small constant tables)
@@ -211,6 +212,44 @@ int jpegds_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int l
 // (1, 2, 4, 8): packed as `layout` at full size, as three ceil(w / shrink) x ceil(h / shrink) planes otherwise
 int jpegrt_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, int quality, int shrink,
                   hipStream_t st);
+// k_jpege.hip: the coefficients k_jpegc writes -> one output slot per image (mipx_jpeg_scan_bytes): the
+// Huffman-coded, padded and stuffed scan behind a 16-byte header.  work: a JpegeWork of (n, w, h), 16-byte aligned
+int jpege_launch(const uint8_t *coefs, uint8_t *out, int n, int w, int h, int layout, uint8_t *work, hipStream_t st);
+// The coder's workspace, sized without the layout (both fit): byte offsets of its parts, each a multiple
+// of 256, and the total.  Per image: cap = 384 ceil(w / 8) ceil(h / 8) bytes, the 4:4:4 coefficients;
+// blocks = the scan's blocks, dummy ones included, of whichever layout has more.
+constexpr int kJpegeTile = 256;     // scan blocks per workgroup of the count and pack kernels
+constexpr int kJpegeChunk = 1024;   // stream bytes per workgroup of the stuffing kernels
+struct JpegeWork {
+    size_t cap, blocks, tiles, chunks;
+    size_t coefs;      // n * cap: k_jpegc's output, when the call starts from RGB
+    size_t info;       // n * 32: per image bits (u64), 0xFF bytes (u32), status (u32), flags (u32)
+    size_t stream;     // n * cap: the scan before stuffing; follows info, one memset clears both
+    size_t counts;     // n * blocks u32: bits per block
+    size_t tile_sums;  // n * tiles u32, then their exclusive scan as u64
+    size_t tile_offs;
+    size_t chunk_sums;  // n * chunks u32, then their exclusive scan as u64
+    size_t chunk_offs;
+    size_t total;
+    JpegeWork(int n, int w, int h) {
+        auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+        const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
+        const size_t mcus = ((ywb + 1) / 2) * ((yhb + 1) / 2), N = static_cast<size_t>(n);
+        cap = 384 * ywb * yhb;
+        blocks = 3 * ywb * yhb > 6 * mcus ? 3 * ywb * yhb : 6 * mcus;
+        tiles = (blocks + kJpegeTile - 1) / kJpegeTile;
+        chunks = (cap + kJpegeChunk - 1) / kJpegeChunk;
+        coefs = 0;
+        info = coefs + up(N * cap);
+        stream = info + up(N * 32);
+        counts = stream + up(N * cap);
+        tile_sums = counts + up(N * blocks * 4);
+        tile_offs = tile_sums + up(N * tiles * 4);
+        chunk_sums = tile_offs + up(N * tiles * 8);
+        chunk_offs = chunk_sums + up(N * chunks * 4);
+        total = chunk_offs + up(N * chunks * 8);
+    }
+};
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,
@@ -225,7 +264,7 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
 // fields already validated): of the file's size, which a scaled step carries in a[2], a[3]
 size_t plan_input_bytes(const mipx_plan *p);
 // bytes per image of the plan's output buffer: out_w * out_h * out_bands, or the coefficients
-// when the last step is MIPX_OP_JPEGC (plan already validated)
+// when the last step is MIPX_OP_JPEGC, or the scan's slot when it is MIPX_OP_JPEGE (plan already validated)
 size_t plan_output_bytes(const mipx_plan *p);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }

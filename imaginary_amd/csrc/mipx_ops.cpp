@@ -30,6 +30,9 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
             const size_t s = p0 > 1.0 ? static_cast<size_t>(p0) : 1;
             return align_up(static_cast<size_t>(n) * ((w + s - 1) / s) * ((h + s - 1) / s) * 3);
         }
+        // the entropy coder's: the coefficients, the scan before stuffing, the per-block and
+        // per-tile bit counts and their scans (JpegeWork); sized without the layout
+        case MIPX_OP_JPEGE: return JpegeWork(n, w, h).total;
         default: return 0;
     }
 }
@@ -160,6 +163,42 @@ int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
         quality < 1 || quality > 100)
         return MIPX_EINVAL;
     return jpegc_launch(d_in, d_out, n, w, h, layout, quality, as_stream(stream));
+}
+
+int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
+                          void *d_work, void *stream) {
+    if (!d_coefs || !d_out || !d_work || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
+        return MIPX_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_work) & 15u) {
+        set_error("jpeg coefficients to scan: the workspace is not 16-byte aligned");
+        return MIPX_EINVAL;
+    }
+    // byte offsets inside an image are 32-bit in the kernels
+    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+        set_error("jpeg coefficients to scan: image %dx%d too large (an image's bytes >= 2^32)", w, h);
+        return MIPX_EUNSUPPORTED;
+    }
+    return jpege_launch(d_coefs, d_out, n, w, h, layout, static_cast<uint8_t *>(d_work), as_stream(stream));
+}
+
+int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
+                             int32_t quality, void *d_work, void *stream) {
+    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
+        quality < 1 || quality > 100)
+        return MIPX_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_work) & 15u) {
+        set_error("rgb to jpeg scan: the workspace is not 16-byte aligned");
+        return MIPX_EINVAL;
+    }
+    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+        set_error("rgb to jpeg scan: image %dx%d too large (an image's bytes >= 2^32)", w, h);
+        return MIPX_EUNSUPPORTED;
+    }
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint8_t *coefs = work + JpegeWork(n, w, h).coefs;  // packed as mipx_jpegc_bytes per image
+    const int e = jpegc_launch(d_in, coefs, n, w, h, layout, quality, as_stream(stream));
+    if (e) return e;
+    return jpege_launch(coefs, d_out, n, w, h, layout, work, as_stream(stream));
 }
 
 int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,

@@ -543,7 +543,8 @@ namespace {
 
 int textmark_index(const mipx_plan *p) {
     int i = p->n_steps;
-    if (i > 0 && p->steps[i - 1].op == MIPX_OP_JPEGC) --i;  // the coefficients are made of the marked image
+    if (i > 0 && (p->steps[i - 1].op == MIPX_OP_JPEGC || p->steps[i - 1].op == MIPX_OP_JPEGE))
+        --i;  // the coefficients, or the scan, are made of the marked image
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_JPEGRT) --i;  // ... and so is the re-encoded one
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_BW) --i;
     if (i > 0 && p->steps[i - 1].op == MIPX_OP_FLATTEN) --i;
@@ -665,9 +666,22 @@ extern "C" size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout) {
     return 128 * (ywb * yhb + 2 * cwb * chb);
 }
 
+extern "C" size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout) {
+    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
+    return coefs ? MIPX_JPEG_SCAN_HEADER_BYTES + coefs : 0;
+}
+
+// whether the plan's last step makes its output something else than pixels
+static bool ends_with_jpeg_output(const mipx_plan *p) {
+    return p->n_steps > 0 &&
+           (p->steps[p->n_steps - 1].op == MIPX_OP_JPEGC || p->steps[p->n_steps - 1].op == MIPX_OP_JPEGE);
+}
+
 size_t mipx::plan_output_bytes(const mipx_plan *p) {
     if (p->n_steps > 0 && p->steps[p->n_steps - 1].op == MIPX_OP_JPEGC)
         return mipx_jpegc_bytes(p->out_w, p->out_h, p->steps[p->n_steps - 1].a[0]);
+    if (p->n_steps > 0 && p->steps[p->n_steps - 1].op == MIPX_OP_JPEGE)
+        return mipx_jpeg_scan_bytes(p->out_w, p->out_h, p->steps[p->n_steps - 1].a[0]);
     return static_cast<size_t>(p->out_w) * p->out_h * p->out_bands;
 }
 
@@ -686,8 +700,8 @@ extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32
                         plan->out_w, plan->out_h, plan->out_bands);
         return MIPX_EINVAL;
     }
-    if (plan->n_steps > 0 && plan->steps[plan->n_steps - 1].op == MIPX_OP_JPEGC) {
-        mipx::set_error("mipx_plan_set_jpegc_output: the plan already gives coefficients");
+    if (ends_with_jpeg_output(plan)) {
+        mipx::set_error("mipx_plan_set_jpegc_output: the plan already gives coefficients or a scan");
         return MIPX_EINVAL;
     }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
@@ -697,6 +711,35 @@ extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32
     mipx_step &s = plan->steps[plan->n_steps++];
     std::memset(&s, 0, sizeof(s));
     s.op = MIPX_OP_JPEGC;
+    s.a[0] = layout, s.a[1] = quality;
+    s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
+    return MIPX_OK;
+}
+
+// ---- entropy-coded JPEG output (MIPX_OP_JPEGE) -----------------------------------------
+extern "C" int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, int32_t quality) {
+    const char *who = "mipx_plan_set_jpeg_scan_output";
+    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (quality < 1 || quality > 100) {
+        mipx::set_error("%s: quality %d outside 1..100", who, quality);
+        return MIPX_EINVAL;
+    }
+    if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
+        mipx::set_error("%s: the plan makes %dx%dx%d, a YCbCr JPEG is of 3 bands", who, plan->out_w, plan->out_h,
+                        plan->out_bands);
+        return MIPX_EINVAL;
+    }
+    if (ends_with_jpeg_output(plan)) {
+        mipx::set_error("%s: the plan already gives coefficients or a scan", who);
+        return MIPX_EINVAL;
+    }
+    if (plan->n_steps >= MIPX_MAX_STEPS) {
+        mipx::set_error("%s: the plan is full (MIPX_MAX_STEPS)", who);
+        return MIPX_EINVAL;
+    }
+    mipx_step &s = plan->steps[plan->n_steps++];
+    std::memset(&s, 0, sizeof(s));
+    s.op = MIPX_OP_JPEGE;
     s.a[0] = layout, s.a[1] = quality;
     s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
     return MIPX_OK;
@@ -725,8 +768,8 @@ extern "C" int mipx_plan_add_jpeg_roundtrip(mipx_plan *plan, int32_t layout, int
                         plan->out_h);
         return MIPX_EINVAL;
     }
-    if (plan->n_steps > 0 && plan->steps[plan->n_steps - 1].op == MIPX_OP_JPEGC) {
-        mipx::set_error("%s: the plan already gives coefficients", who);
+    if (ends_with_jpeg_output(plan)) {
+        mipx::set_error("%s: the plan already gives coefficients or a scan", who);
         return MIPX_EINVAL;
     }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
@@ -834,6 +877,10 @@ extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_p
             }
             if (k + 1 < n_stages && s.steps[i].op == MIPX_OP_JPEGC) {  // only the request's output can be coefficients
                 mipx::set_error("mipx_plan_chain: stage %d gives coefficients; only the last stage may", k);
+                return MIPX_EINVAL;
+            }
+            if (k + 1 < n_stages && s.steps[i].op == MIPX_OP_JPEGE) {  // ... or an entropy-coded scan
+                mipx::set_error("mipx_plan_chain: stage %d gives a scan; only the last stage may", k);
                 return MIPX_EINVAL;
             }
         }

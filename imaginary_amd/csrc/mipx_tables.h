@@ -70,5 +70,10 @@ HostTable build_bicubic_table();
 // m | q << 21 with m = ceil(2^kJpegcRecipShift / q): (n * m) >> kJpegcRecipShift == n / q for
 // every n < 2^12, so ((c + 4 q) >> 3) through it is (c + 4 q) / (8 q) for c + 4 q < 2^15
 HostTable build_jpegc_recips(int quality);
+// k_jpege's Huffman codes, canonical (Annex C) from the code counts and symbols of Annex K.3:
+// [DC lum | AC lum | DC chr | AC chr], kJpegeCodesPerTable uint32 each, indexed by the symbol (a DC
+// category 0..11, or an AC run << 4 | size), each length << 16 | code; 0 where the table has no code
+constexpr int kJpegeCodesPerTable = 256;
+HostTable build_jpege_codes();
 
 }  // namespace mipx

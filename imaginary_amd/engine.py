@@ -11,7 +11,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, YCC_444, YCC_420, sync_tuning)
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, YCC_444, YCC_420,
+                   JPEG_SCAN_HEADER_BYTES, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
@@ -19,6 +20,7 @@ __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
+           "plan_set_jpeg_scan_output", "jpeg_scan_bytes", "rgb_to_jpeg_scan", "jpegc_to_scan", "scan_slot",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -377,6 +379,38 @@ def _jpegc_layout(plan: MipxPlan):
     return last.a[0] if last is not None and last.op == OP_JPEGC else None
 
 
+def jpeg_scan_bytes(w: int, h: int, layout: int) -> int:
+    """mipx_jpeg_scan_bytes: bytes of one image's entropy-coded output slot (0 for bad arguments)."""
+    return int(lib.mipx_jpeg_scan_bytes(w, h, layout))
+
+
+def plan_set_jpeg_scan_output(plan: MipxPlan, layout: int, quality: int) -> MipxPlan:
+    """mipx_plan_set_jpeg_scan_output on `plan` (in place; returned for convenience): the plan then
+    gives the finished entropy-coded scan of its 3-band result (YCC_444 or YCC_420, made at
+    `quality`), one slot per image (scan_slot reads it), instead of RGB pixels."""
+    check(lib.mipx_plan_set_jpeg_scan_output(C.byref(plan), layout, quality), "mipx_plan_set_jpeg_scan_output")
+    return plan
+
+
+def _jpege_layout(plan: MipxPlan):
+    """The layout of the scan a plan gives, or None for anything else."""
+    last = plan.steps[plan.n_steps - 1] if plan.n_steps > 0 else None
+    return last.a[0] if last is not None and last.op == OP_JPEGE else None
+
+
+def scan_slot(slot):
+    """(status, bits, scan) of one output slot of MIPX_OP_JPEGE (uint8, jpeg_scan_bytes long):
+    scan is the `length` bytes behind the header, empty unless status is 0 (codec.jpeg_from_scan
+    makes the file of it)."""
+    slot = np.ascontiguousarray(slot, dtype=np.uint8).ravel()
+    length, status, bits, _ = (int(v) for v in slot[:JPEG_SCAN_HEADER_BYTES].view("<u4"))
+    if status != 0:
+        return status, bits, b""
+    if length > slot.size - JPEG_SCAN_HEADER_BYTES:
+        raise ValueError(f"slot of {slot.size} bytes says its scan has {length}")
+    return status, bits, slot[JPEG_SCAN_HEADER_BYTES:JPEG_SCAN_HEADER_BYTES + length].tobytes()
+
+
 def fit_dimension(iw, ih, fw, fh):
     a, b = C.c_int32(), C.c_int32()
     check(lib.mipx_fit_dimension(iw, ih, fw, fh, C.byref(a), C.byref(b)), "mipx_fit_dimension")
@@ -430,8 +464,11 @@ class Engine:
                   and img.strides[1] == img.shape[2]):
             img = np.ascontiguousarray(img, dtype=np.uint8)  # rows may keep a wider stride
         coefs = _jpegc_layout(plan)
+        scan = _jpege_layout(plan)
         if coefs is not None:  # the coefficients of one image, described as the plan's w x h x 3
             shape, dtype = (jpegc_bytes(plan.out_w, plan.out_h, coefs) // 2,), np.int16
+        elif scan is not None:  # ... or its slot
+            shape, dtype = (jpeg_scan_bytes(plan.out_w, plan.out_h, scan),), np.uint8
         else:
             shape, dtype = (plan.out_h, plan.out_w, plan.out_bands), np.uint8
         if out is None:
@@ -442,7 +479,8 @@ class Engine:
         wm = np.ascontiguousarray(wm, dtype=np.uint8) if wm is not None else None  # a copy must live until the submit
         wmi = C.byref(_img(wm)) if wm is not None else None
         src = MipxImg(img.ctypes.data, plan.in_w, plan.in_h, 3, 0) if planar else _img(img)
-        dst = MipxImg(out.ctypes.data, plan.out_w, plan.out_h, 3, 0) if coefs is not None else _img(out)
+        packed = coefs is not None or scan is not None
+        dst = MipxImg(out.ctypes.data, plan.out_w, plan.out_h, 3, 0) if packed else _img(out)
         check(lib.mipx_submit(device, C.byref(plan), C.byref(src), wmi, C.byref(dst),
                               C.byref(ti)), "mipx_submit")
         return ti.value, out
@@ -621,6 +659,46 @@ def rgb_to_jpegc(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
     return dout.download((n, need // 2), np.int16)
 
 
+def rgb_to_jpeg_scan(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
+    """mipx_op_rgb_to_jpeg_scan on (h, w, 3) or (n, h, w, 3) uint8; returns the slots,
+    (n, jpeg_scan_bytes) uint8."""
+    sync_tuning()
+    x = _batch(imgs)
+    n, h, w, b = x.shape
+    need = jpeg_scan_bytes(w, h, layout)
+    if b != 3 or need == 0:
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
+    what = "mipx_op_rgb_to_jpeg_scan"
+    din = _dev("in", what, x.nbytes, w * 3, x)
+    dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
+    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 0.0, 0.0))
+    check(lib.mipx_op_rgb_to_jpeg_scan(din.ptr, dout.ptr, n, w, h, layout, quality, ws.ptr, None), what)
+    synchronize()
+    _check_guards(what, din, dout, ws)
+    return dout.download((n, need))
+
+
+def jpegc_to_scan(coefs: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
+    """mipx_op_jpegc_to_scan on coefficients as rgb_to_jpegc returns them, (jpegc_bytes / 2,) or
+    (n, jpegc_bytes / 2) int16; returns the slots, (n, jpeg_scan_bytes) uint8."""
+    sync_tuning()
+    x = np.ascontiguousarray(coefs, dtype=np.int16)
+    if x.ndim == 1:
+        x = x[None]
+    have = jpegc_bytes(w, h, layout)
+    if x.ndim != 2 or have == 0 or x.shape[1] * 2 != have:
+        raise ValueError(f"coefficients of shape {np.shape(coefs)} for {w}x{h} layout {layout}: {have // 2} per image")
+    n, need = x.shape[0], jpeg_scan_bytes(w, h, layout)
+    what = "mipx_op_jpegc_to_scan"
+    din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x.view(np.uint8))
+    dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
+    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 0.0, 0.0))
+    check(lib.mipx_op_jpegc_to_scan(din.ptr, dout.ptr, n, w, h, layout, ws.ptr, None), what)
+    synchronize()
+    _check_guards(what, din, dout, ws)
+    return dout.download((n, need))
+
+
 def jpegd_to_rgb(payload: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
     """mipx_op_jpegd_to_rgb on coefficient payloads, (bytes,) or (n, bytes) uint8; returns (n, h, w, 3)."""
     sync_tuning()
@@ -706,7 +784,8 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
     """mipx_execute_dev on a batch of host images (uploads, runs the plan, downloads); for a
     plan that takes planar input (plan_set_ycc_input), on packed planes, (bytes,) or (n, bytes),
     and for one that takes coefficient input (plan_set_jpegd_input[_scaled]), on payloads of the same shapes;
-    a plan that gives coefficients (plan_set_jpegc_output) returns (n, jpegc_bytes / 2) int16.
+    a plan that gives coefficients (plan_set_jpegc_output) returns (n, jpegc_bytes / 2) int16, one
+    that gives scans (plan_set_jpeg_scan_output) the slots, (n, jpeg_scan_bytes) uint8.
     junk: fill the workspace (the ping-pong intermediates) and the output with this byte
     first, so a step that reads outside what the steps before it wrote shows up."""
     sync_tuning()
@@ -716,7 +795,10 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
     what = "mipx_execute_dev"
     din = _dev("in", what, x.nbytes, plan.in_w if planar else x.shape[2] * x.shape[3], x)
     coefs = _jpegc_layout(plan)
+    scan = _jpege_layout(plan)
     out1 = jpegc_bytes(plan.out_w, plan.out_h, coefs) if coefs is not None else plan.out_w * plan.out_h * plan.out_bands
+    if scan is not None:
+        out1 = jpeg_scan_bytes(plan.out_w, plan.out_h, scan)
     dout = _dev("out", what, n * out1, plan.out_w * plan.out_bands)
     wsb = lib.mipx_workspace_bytes(C.byref(plan), n)
     ws = _dev("ws", what, wsb) if wsb else None
@@ -734,6 +816,8 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
     _check_guards(what, din, dout, dwm, ws)
     if coefs is not None:
         return dout.download((n, out1 // 2), np.int16)
+    if scan is not None:
+        return dout.download((n, out1))
     return dout.download((n, plan.out_h, plan.out_w, plan.out_bands))
 
 

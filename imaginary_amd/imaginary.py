@@ -29,7 +29,8 @@ import numpy as np
 
 from . import _abi, codec
 from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_jpeg_roundtrip, plan_add_textmark,
-                     plan_chain, plan_make, plan_set_jpegc_output, plan_set_jpegd_input, plan_set_jpegd_input_scaled, plan_set_ycc_input, plan_textmark_geometry)
+                     plan_chain, plan_make, plan_set_jpeg_scan_output, plan_set_jpegc_output, plan_set_jpegd_input,
+                     plan_set_jpegd_input_scaled, plan_set_ycc_input, plan_textmark_geometry, scan_slot)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -490,9 +491,20 @@ class JpegCoefs:
     quality: int
 
 
+@dataclass
+class JpegScan:
+    """What process(..., jpeg_quality=q, jpeg_scan=True) returns in place of pixels: the finished
+    entropy-coded scan of the w x h result (codec.jpeg_from_scan writes the file)."""
+    scan: bytes
+    w: int
+    h: int
+    layout: int
+    quality: int
+
+
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
             text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None,
-            jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False):
+            jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False, jpeg_scan: bool = False):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -514,7 +526,9 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     called.
     With `jpeg_quality` (1..100) and a 3-band result, the plan ends with the coefficient step
     (4:2:0 below Q 90, 4:4:4 from Q 90, as codec.encode samples) and a JpegCoefs is returned;
-    results of other band counts come back as pixels."""
+    results of other band counts come back as pixels.  With `jpeg_scan` too, the plan ends with the
+    entropy-coding step instead and a JpegScan is returned; a slot that reports an overflow or an
+    uncodable coefficient makes the request run again with the coefficient step."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         return process_bytes(bytes(img), opts, wm, text)
     if isinstance(img, _Staged):
@@ -561,6 +575,13 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
             return _placeholder(plan.out_h, plan.out_w, plan.out_bands)
         if jpeg_quality is not None and plan.out_bands == 3:
             layout = codec.YCC_444 if jpeg_quality >= 90 else codec.YCC_420
+            if jpeg_scan:
+                coded = _abi.MipxPlan()
+                C.memmove(C.byref(coded), C.byref(plan), C.sizeof(plan))
+                plan_set_jpeg_scan_output(coded, layout, jpeg_quality)
+                status, _, scan = scan_slot(_run(coded, px, wm))
+                if status == _abi.JPEG_SCAN_OK:
+                    return JpegScan(scan, plan.out_w, plan.out_h, layout, jpeg_quality)
             plan_set_jpegc_output(plan, layout, jpeg_quality)
             return JpegCoefs(_run(plan, px, wm), plan.out_w, plan.out_h, layout, jpeg_quality)
         return _run(plan, px, wm)
@@ -572,7 +593,7 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
-                  jpeg_dct_shrink: bool = False, device_reencode: bool = False) -> Image:
+                  jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -582,6 +603,10 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     jpeg_coefs: when the answer is a JPEG of a 3-band image, let the engine run the encoder's
     colour conversion, downsampling, DCT and quantisation too and only entropy-code on the host
     (codec.encode_jpeg_coefs); the scan is the same either way.  Other outputs keep the RGB path.
+    jpeg_scan: when the answer is a JPEG of a 3-band image, let the engine entropy-code it as well: the
+    plan ends with MIPX_OP_JPEGE and the host only writes the header in front of the scan and EOI
+    behind it (codec.jpeg_from_scan); a slot the engine could not fill runs again as `jpeg_coefs`.
+    The bytes are the same either way.  Other outputs keep the RGB path.
     jpeg_dct: hand a baseline 4:4:4 or 4:2:0 YCbCr JPEG to the engine as its quantisation tables and
     quantised coefficients (codec.decode_jpeg_coefs), so the host only entropy-decodes, when the
     request decodes at full size; the bytes are the same either way.  Shrink-on-load requests, the
@@ -609,7 +634,7 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     itype = hdr.type if hdr.type in _abi.TYPES else "unknown"
     t = out_type or (hdr.type if hdr.type in ("jpeg", "png", "webp", "gif", "tiff") else "png")
     q = quality or codec.DEFAULT_QUALITY
-    jq = q if jpeg_coefs and t == "jpeg" and 1 <= q <= 100 else None   # process() looks at the bands
+    jq = q if (jpeg_coefs or jpeg_scan) and t == "jpeg" and 1 <= q <= 100 else None   # process() looks at the bands
     if wm_px is not None:
         opts = dict(opts, wm_enable=1)
     # plan on the header first: the decode depends on the plan's shrink-on-load
@@ -630,19 +655,22 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         dct = codec.decode_jpeg_coefs(buf) if take else None
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
         px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
-                     jpeg_dct_shrink=dct is not None)
+                     jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan)
     else:
         dct = codec.decode_jpeg_coefs(buf) if jpeg_dct and hdr.bands == 3 and itype == "jpeg" else None
         planes = codec.decode_ycc(buf) if dct is None and ycc and hdr.bands == 3 else None
         if dct is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         jpeg_dct=dct, jpeg_quality=jq)
+                         jpeg_dct=dct, jpeg_quality=jq, jpeg_scan=jpeg_scan)
         elif planes is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         ycc=planes, jpeg_quality=jq)
+                         ycc=planes, jpeg_quality=jq, jpeg_scan=jpeg_scan)
         else:
             px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         jpeg_quality=jq)
+                         jpeg_quality=jq, jpeg_scan=jpeg_scan)
+    if isinstance(px, JpegScan):
+        body = codec.jpeg_from_scan(px.scan, px.w, px.h, px.layout, px.quality)
+        return Image(body, codec.mime_type(codec.sniff_type(body)))
     if isinstance(px, JpegCoefs):
         body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)
         return Image(body, codec.mime_type(codec.sniff_type(body)))

@@ -40,6 +40,8 @@
  *    input bytes instead (packed JPEG planes, see MIPX_YCC_*), at any alignment.
  *    A plan that ends with MIPX_OP_JPEGC, and mipx_op_rgb_to_jpegc, write n * mipx_jpegc_bytes()
  *    output bytes instead (JPEG coefficients), at any alignment.
+ *    A plan that ends with MIPX_OP_JPEGE, mipx_op_rgb_to_jpeg_scan and mipx_op_jpegc_to_scan write
+ *    n * mipx_jpeg_scan_bytes() output bytes instead (entropy-coded scans), at any alignment.
  *    A plan that starts with MIPX_OP_JPEGD, and mipx_op_jpegd_to_rgb, read n * mipx_jpegd_bytes()
  *    input bytes instead (quantisation tables + JPEG coefficients), at any alignment.
  *  - Thread-safe: mipx_submit / mipx_wait / mipx_process may be called from
@@ -150,11 +152,16 @@ enum {
                             the payload is that file's, and the plan's in_w x in_h must be
                             ceil(a[2] / a[1]) x ceil(a[3] / a[1]) (mipx_plan_set_jpegd_input_scaled);
                             any other a[1] is MIPX_EINVAL */
-    MIPX_OP_JPEGRT       /* = 18, the JPEG round trip: a[0] = MIPX_YCC_*, a[1] = quality 1..100, a[2] = shrink
+    MIPX_OP_JPEGRT,      /* = 18, the JPEG round trip: a[0] = MIPX_YCC_*, a[1] = quality 1..100, a[2] = shrink
                             (0 or 1 full size; 2, 4, 8); on a 3-band image at any index of a plan; out =
                             ceil(w / shrink) x ceil(h / shrink) x 3: the pixels the JPEG of the image at that
                             quality decodes to at that scale (mipx_plan_add_jpeg_roundtrip)
                                   (MIPX_OP_JPEGC's rule, then MIPX_OP_JPEGD's with the same tables) */
+    MIPX_OP_JPEGE        /* = 19, the entropy-coded scan: a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/
+                            out_bands = the image it consumes (w, h, 3); only as the LAST step of a plan whose
+                            image there has 3 bands, never together with MIPX_OP_JPEGC; the output buffer is
+                            then one slot per image (mipx_plan_set_jpeg_scan_output)
+                                  (MIPX_OP_JPEGC's rule, then libjpeg's baseline Huffman coder) */
 };
 
 /* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
@@ -205,6 +212,29 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * exactly MIPX_OP_JPEGD's rule on those coefficients at scale 1 / shrink with the tables of
  * jpeg_set_quality(quality, TRUE).  Blocks are independent, so the coefficients stay on the chip.
  * Bit for bit libjpeg-turbo's encode -> decode (PARITY_ASSUMPTIONS.md row 20). */
+/* Entropy-coded JPEG output (MIPX_OP_JPEGE): the finished scan of a baseline JPEG, so the host only
+ * writes the header in front (SOI to SOS: a function of w, h, layout and quality) and FF D9 behind.
+ * The engine codes exactly MIPX_OP_JPEGC's coefficients (PARITY_ASSUMPTIONS.md row 21): one
+ * interleaved scan without restart markers; the four Huffman tables of Annex K.3, Y with tables
+ * 0/0, Cb and Cr with 1/1; MCU order Y Cb Cr (4:4:4) or Y00 Y01 Y10 Y11 Cb Cr (4:2:0) over
+ * ceil(w / 16) x ceil(h / 16) MCUs; libjpeg's dummy blocks where the Y blocks do not fill the
+ * MCUs (zero AC; the DC of the block to the left or, in a wholly dummy block row, of the last block
+ * of the same MCU's row above); bits packed most significant first, the last byte padded with
+ * 1-bits, every 0xFF byte followed by 0x00.
+ *    One image's output is a slot of mipx_jpeg_scan_bytes(w, h, layout) = 16 +
+ * mipx_jpegc_bytes(w, h, layout) bytes: four little-endian uint32 (length, status, bits, 0), then
+ * `length` scan bytes; the slot's bytes behind them are unspecified.  bits is the scan's length in
+ * bits before padding and stuffing (saturating at 2^32 - 1).  status MIPX_JPEG_SCAN_OK: the scan is
+ * there.  MIPX_JPEG_SCAN_OVERFLOW: it does not fit the slot; length is then ceil(bits / 8), a lower
+ * bound of the need, the data bytes are unspecified, and the caller asks for coefficients instead
+ * (a coefficient can cost 26 bits and stuffing can double them, so no capacity short of about 416
+ * bytes per block excludes this; the slot keeps the size of the coefficients it replaces).
+ * MIPX_JPEG_SCAN_UNCODABLE: a coefficient has no Annex K code (an AC magnitude above 1023 or a DC
+ * difference above 2047 in magnitude, which MIPX_OP_JPEGC never makes of 8-bit pixels); length is 0;
+ * it wins over OVERFLOW.  Nothing outside the slot is ever written; slots and both pointers start
+ * on any byte. */
+#define MIPX_JPEG_SCAN_HEADER_BYTES 16
+enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODABLE = 2 };
 #define MIPX_JPEGD_HEADER_BYTES 384
 
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
@@ -310,6 +340,21 @@ int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout);
 size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout);
 int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32_t quality);
 int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
+/* Entropy-coded JPEG output (MIPX_OP_JPEGE, see MIPX_JPEG_SCAN_HEADER_BYTES).  Both calls work
+ * without a GPU.
+ * mipx_jpeg_scan_bytes: bytes of one w x h image's output slot, 16 + mipx_jpegc_bytes(w, h,
+ * layout); 0 for a non-positive size or an unknown layout.
+ * mipx_plan_set_jpeg_scan_output: appends the MIPX_OP_JPEGE step to a plan whose output has 3
+ * bands.  The plan's geometry is unchanged; the output buffer is then mipx_jpeg_scan_bytes(out_w,
+ * out_h, layout) bytes per image for mipx_execute_dev, and for mipx_submit a mipx_img of w = out_w,
+ * h = out_h, bands = 3, stride = 0 whose data has that many bytes (anything else is MIPX_EINVAL).
+ * Composition rules and MIPX_EINVAL cases are mipx_plan_set_jpegc_output's: last step only, last
+ * chain stage only, after planar or coefficient input, a text watermark and a round trip in either
+ * call order; and MIPX_EINVAL for a plan that already ends with MIPX_OP_JPEGC or MIPX_OP_JPEGE
+ * (mipx_plan_set_jpegc_output and mipx_plan_add_jpeg_roundtrip likewise refuse a plan that ends
+ * with MIPX_OP_JPEGE).  The request path copies whole slots to the host. */
+size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout);
+int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, int32_t quality);
 /* JPEG coefficient input (MIPX_OP_JPEGD, see MIPX_JPEGD_HEADER_BYTES).  Both calls work without a GPU.
  * mipx_jpegd_bytes: bytes of one w x h image's payload, 384 + mipx_jpegc_bytes(w, h, layout); 0
  * for a non-positive size or an unknown layout.
@@ -428,6 +473,20 @@ int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w
  * are 32-bit).  No workspace. */
 int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                          int32_t layout, int32_t quality, void *stream);
+/* The entropy coder (MIPX_OP_JPEGE): n images of JPEG coefficients, as mipx_op_rgb_to_jpegc writes
+ * them, -> n slots (n * mipx_jpeg_scan_bytes(w, h, layout) bytes); any int16 values are legal input
+ * (see MIPX_JPEG_SCAN_UNCODABLE).  mipx_op_rgb_to_jpeg_scan runs mipx_op_rgb_to_jpegc into the
+ * workspace first.  Input and output pointers at any alignment.  d_work: 16-byte aligned device
+ * memory of mipx_op_workspace_bytes(MIPX_OP_JPEGE, n, w, h, 3, 0, 0) bytes (the coefficients, the scan
+ * before stuffing, bit counts per block and their sums: about 12.3 bytes per pixel, sized for 4:4:4).  A call is a
+ * memset and six launches; every dependency between workgroups is a launch boundary.  MIPX_EINVAL,
+ * before any HIP call, for NULL pointers, n <= 0, a non-positive size, an unknown layout, a quality
+ * outside 1..100 or a misaligned workspace; MIPX_EUNSUPPORTED for an image whose payload or RGB is
+ * 2^32 bytes or more, as for mipx_op_jpegd_to_rgb. */
+int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                          int32_t layout, void *d_work, void *stream);
+int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                             int32_t layout, int32_t quality, void *d_work, void *stream);
 /* n payloads (n * mipx_jpegd_bytes(w, h, layout) bytes) -> n x h x w x 3 RGB; both pointers at any
  * alignment.  The workspace takes the decoded planes between the two launches (inverse DCT, then
  * the MIPX_OP_YCC kernels): mipx_op_workspace_bytes(MIPX_OP_JPEGD, n, w, h, 3, 0, 0) bytes.

@@ -9,8 +9,11 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpegd420 --w 3840 --h 2160 --n 64 --q 75
     python scripts/op_bench.py jpegds420 --w 3840 --h 2160 --n 64 --q 75 --shrink 4
     python scripts/op_bench.py jpegrt420 --w 3840 --h 2160 --n 64 --q 75
+    python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75     (RGB -> entropy-coded scan)
+    python scripts/op_bench.py jpegcs420 --w 3840 --h 2160 --n 64 --q 75    (the entropy coder alone)
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
          jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444 jpegrt420 jpegrt444
+         jpege420 jpege444 jpegcs420 jpegcs444
 """
 import argparse
 import ctypes as C
@@ -114,11 +117,26 @@ def main():
         layout = 1 if a.op == "jpegrt420" else 0
         ow, oh = -(-w // a.shrink), -(-h // a.shrink)
         in_img, out_img = w * h * 3, ow * oh * 3
+    JPEGE = ("jpege420", "jpege444", "jpegcs420", "jpegcs444")
+    if a.op in JPEGE:   # RGB (jpege*) or the encoder's coefficients (jpegcs*) in, one slot per image out
+        b = ob = 3
+        layout = 1 if a.op.endswith("420") else 0
+        in_img = w * h * 3 if a.op.startswith("jpege") else lib.mipx_jpegc_bytes(w, h, layout)
+        out_img = lib.mipx_jpeg_scan_bytes(w, h, layout)
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
     y = torch.empty((n * out_img,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
+    if a.op in JPEGE:
+        ws = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
+    if a.op in ("jpegcs420", "jpegcs444"):
+        # the coefficients the engine's own encoder makes of random pixels at --q, as for jpegd*
+        px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        assert lib.mipx_op_rgb_to_jpegc(px.data_ptr(), x.data_ptr(), n, w, h, layout, a.q, None) == 0
+        check(lib.mipx_device_sync())
+        del px
     if a.op in JPEGD:
         # what a decoder hands over: the coefficients the engine's own encoder makes of random pixels
         # at --q (zero runs and small values, not noise), behind that quality's tables
@@ -179,6 +197,10 @@ def main():
             return lib.mipx_op_jpegd_to_rgb_scaled(X, Y, n, w, h, layout, a.shrink, WS, WSB, sp)
         if a.op in ("jpegrt420", "jpegrt444"):
             return lib.mipx_op_jpeg_roundtrip(X, Y, n, w, h, layout, a.q, a.shrink, WS, WSB, sp)
+        if a.op in ("jpege420", "jpege444"):
+            return lib.mipx_op_rgb_to_jpeg_scan(X, Y, n, w, h, layout, a.q, WS, sp)
+        if a.op in ("jpegcs420", "jpegcs444"):
+            return lib.mipx_op_jpegc_to_scan(X, Y, n, w, h, layout, WS, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -213,6 +235,10 @@ def main():
         line["shrink"] = a.shrink
     if not a.ab:
         ms = measure()
+        if a.op in JPEGE:   # what the slots say: the scans' mean length against the slot's capacity
+            head = y.view(n, out_img)[:, :16].cpu().numpy().view("<u4")
+            line.update(q=a.q, capacity=out_img - 16, mean_length=round(float(head[:, 0].mean()), 1),
+                        statuses=sorted(set(head[:, 1].tolist())))
         print(json.dumps({**line, "ms": round(ms, 4), "alg_GBps": round(alg / ms / 1e6, 1)}))
         return
     # same-process A/B: --ab KNOB=v1,v2,... interleaved over 2 rounds, output checked equal
