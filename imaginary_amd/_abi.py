@@ -23,6 +23,7 @@ MIPX_ETIMEOUT = -6
 MIPX_ENOTINIT = -7
 MIPX_ESTALE = -8
 MIPX_EBUSY = -9
+MIPX_EDATA = -10   # a MIPX_OP_JPEGH request whose scan the device could not decode
 
 GRAVITY = {"centre": 0, "north": 1, "east": 2, "south": 3, "west": 4, "smart": 5}
 EXTEND = {"black": 0, "copy": 1, "repeat": 2, "mirror": 3, "white": 4, "background": 5, "lastpixel": 6}
@@ -30,14 +31,17 @@ TYPES = {"unknown": 0, "jpeg": 1, "webp": 2, "png": 3, "tiff": 4, "gif": 5, "pdf
          "magick": 8, "heif": 9, "avif": 10}
 
 (OP_ROT, OP_FLIP, OP_SHRINK, OP_REDUCE, OP_EXTRACT, OP_EMBED, OP_SMARTCROP, OP_BLUR, OP_WATERMARK,
- OP_AFFINE, OP_ZOOM, OP_FLATTEN, OP_BW, OP_TEXTMARK, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE) = range(1, 20)
+ OP_AFFINE, OP_ZOOM, OP_FLATTEN, OP_BW, OP_TEXTMARK, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE,
+ OP_JPEGH) = range(1, 21)
 OP_NAMES = {OP_ROT: "rot", OP_FLIP: "flip", OP_SHRINK: "shrink", OP_REDUCE: "reduce",
             OP_EXTRACT: "extract", OP_EMBED: "embed", OP_SMARTCROP: "smartcrop",
             OP_BLUR: "blur", OP_WATERMARK: "watermark", OP_AFFINE: "affine", OP_ZOOM: "zoom",
             OP_FLATTEN: "flatten", OP_BW: "bw", OP_TEXTMARK: "textmark", OP_YCC: "ycc", OP_JPEGC: "jpegc",
-            OP_JPEGD: "jpegd", OP_JPEGRT: "jpegrt", OP_JPEGE: "jpege"}
+            OP_JPEGD: "jpegd", OP_JPEGRT: "jpegrt", OP_JPEGE: "jpege", OP_JPEGH: "jpegh"}
 JPEG_SCAN_HEADER_BYTES = 16   # MIPX_JPEG_SCAN_HEADER_BYTES: length, status, bits, 0 as little-endian uint32
 JPEG_SCAN_OK, JPEG_SCAN_OVERFLOW, JPEG_SCAN_UNCODABLE = 0, 1, 2   # MIPX_JPEG_SCAN_*
+JPEGH_HEADER_BYTES = 1504     # MIPX_JPEGH_HEADER_BYTES: length, tables, then the file's entropy-coded scan
+JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
 YCC_444 = 0   # planar JPEG input, coefficient input and output (MIPX_YCC_*): Cb, Cr at full size ...
 YCC_420 = 1   # ... or at ceil(w / 2) x ceil(h / 2)
 INTERPRETATION_SRGB = 22
@@ -167,6 +171,12 @@ _SIG = {
     "mipx_op_rgb_to_jpegc": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P]),
     "mipx_op_jpegc_to_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, _P]),
     "mipx_op_rgb_to_jpeg_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P]),
+    "mipx_jpegh_bytes": (C.c_size_t, [_I, _I, _I]),
+    "mipx_plan_set_jpegh_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
+    "mipx_plan_set_jpegh_input_scaled": (C.c_int, [C.POINTER(MipxPlan), _I, _I, _I, _I]),
+    "mipx_op_jpegh_to_jpegd": (C.c_int, [_U8P, _U8P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "mipx_op_jpegh_to_rgb": (C.c_int, [_U8P, _U8P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "mipx_op_jpegh_to_rgb_scaled": (C.c_int, [_U8P, _U8P, _P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_jpegd_to_rgb": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_jpegd_to_rgb_scaled": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mipx_op_jpeg_roundtrip": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),

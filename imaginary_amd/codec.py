@@ -405,10 +405,11 @@ def _huff_lookup(counts, symbols):
     return lut.tolist()
 
 
-def _jpeg_segments(buf: bytes):
+def _jpeg_segments(buf: bytes, dht=None):
     """What decode_jpeg_coefs needs of a file's headers, or None for a file it does not take:
     (w, h, components [(id, h, v, tq, td, ta)], tables {tq: 64 natural-order values}, Huffman
-    lookups {Tc/Th byte: lookup}, restart interval, the entropy-coded intervals)."""
+    lookups {Tc/Th byte: lookup}, restart interval, the entropy-coded intervals).  dht: a dict
+    that takes the Huffman tables as the file has them, {Tc/Th byte: (16 counts, symbols)}."""
     import re
     if buf[:2] != b"\xff\xd8":
         return None
@@ -449,6 +450,8 @@ def _jpeg_segments(buf: bytes):
                 huff[body[0]] = _huff_lookup(body[1:17], body[17:17 + cnt])
                 if huff[body[0]] is None:
                     return None
+                if dht is not None:
+                    dht[body[0]] = (bytes(body[1:17]), bytes(body[17:17 + cnt]))
                 body = body[17 + cnt:]
         elif m in (0xC0, 0xC1):                         # baseline, extended sequential; Huffman
             if frame is not None or len(body) < 6 or body[0] != 8 or body[5] != 3 or len(body) != 6 + 9:
@@ -597,7 +600,54 @@ def decode_jpeg_coefs(buf: bytes):
         return None
 
 
-_SANS_FACES = ("DejaVuSans.ttf", "LiberationSans-Regular.ttf", "NotoSans-Regular.ttf", "FreeSans.ttf", "Arial.ttf")
+# ---- the entropy-coded scan of a JPEG (the engine's entropy decoder, MIPX_OP_JPEGH) ---------
+JPEGH_HEADER_BYTES = 1504   # MIPX_JPEGH_HEADER_BYTES
+JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
+
+
+def jpeg_huff_slot(buf: bytes):
+    """A JPEG's entropy-coded scan as the file has it, packed for the engine's entropy decoder
+    (MIPX_JPEGH_HEADER_BYTES in include/mipx.h): (slot, layout) with slot a 1-D uint8 array of
+    the scan's length, the quantisation tables of Y, Cb, Cr, the components' Huffman table
+    indices, the four Huffman tables and the scan bytes, padded with zeros to the slot's size
+    (1504 + the coefficients' size; slot[:1504 + length] is all the engine reads).  The host
+    reads markers only.  None (it never raises) for every file decode_jpeg_coefs does not take
+    by its headers, and for files with a restart interval, a Huffman table index above 1 or a
+    scan longer than the coefficients."""
+    try:
+        dht = {}
+        seg = _jpeg_segments(bytes(buf), dht)
+        if seg is None:
+            return None
+        w, h, comps, qt, _, restart, parts = seg
+        samp = tuple((c[1], c[2]) for c in comps)
+        layout = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}.get(samp)
+        if layout is None or restart != 0 or len(parts) != 1:
+            return None
+        if any(c[4] > 1 or (c[5] & 15) > 1 for c in comps):
+            return None
+        geo, _, _ = _jpegc_geometry(w, h, layout)
+        cap = 128 * sum(wb * hb for wb, hb, _ in geo)
+        scan = parts[0]
+        if len(scan) > cap:
+            return None
+        slot = np.zeros(JPEGH_HEADER_BYTES + cap, np.uint8)
+        slot[0:4] = np.frombuffer(len(scan).to_bytes(4, "little"), np.uint8)
+        slot[16:400] = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel().view(np.uint8)
+        slot[400:406] = [c[4] for c in comps] + [c[5] & 15 for c in comps]
+        for i, key in enumerate((0x00, 0x01, 0x10, 0x11)):
+            if key in dht:
+                counts, symbols = dht[key]
+                at = 416 + 272 * i
+                slot[at:at + 16] = np.frombuffer(counts, np.uint8)
+                slot[at + 16:at + 16 + len(symbols)] = np.frombuffer(symbols, np.uint8)
+        slot[JPEGH_HEADER_BYTES:JPEGH_HEADER_BYTES + len(scan)] = np.frombuffer(scan, np.uint8)
+        return slot, layout
+    except Exception:  # noqa: BLE001 - whatever this cannot read, the other decoders report
+        return None
+
+
+_SANS_FACES =("DejaVuSans.ttf", "LiberationSans-Regular.ttf", "NotoSans-Regular.ttf", "FreeSans.ttf", "Arial.ttf")
 DEFAULT_FONT_POINTS = 10.0
 
 

@@ -250,6 +250,63 @@ struct JpegeWork {
         total = chunk_offs + up(N * chunks * 8);
     }
 };
+// k_jpegh.hip: n input slots (mipx_jpegh_bytes: header, Huffman tables, the file's entropy-coded scan) ->
+// n payloads of MIPX_OP_JPEGD (mipx_jpegd_bytes) and n statuses (MIPX_JPEGH_*, 4-byte aligned).
+// work: a JpeghWork of (n, w, h), 16-byte aligned; its parts before `payload` are the decoder's own
+int jpegh_launch(const uint8_t *slots, uint8_t *payloads, uint32_t *status, int n, int w, int h, int layout,
+                 uint8_t *work, hipStream_t st);
+constexpr int kJpeghHeader = MIPX_JPEGH_HEADER_BYTES;
+constexpr int kJpeghSub = 128;   // bytes of unstuffed stream per lane of the decoding kernels
+constexpr int kJpeghSeq = 256;   // lanes, so subsequences, per workgroup: a sequence is 32 KiB
+constexpr int kJpeghRounds = 2;  // launches that carry states across sequences, after the first
+// The decoder's workspace, sized without the layout like JpegeWork: byte offsets of its parts, each a
+// multiple of 256, and the total.  The statuses lead, so a plan's caller finds them at the head.
+struct JpeghWork {
+    size_t cap, blocks, tiles, chunks, seqs, sstride;
+    size_t status;      // n u32: MIPX_JPEGH_* per image
+    size_t info;        // n * 32: per image the unstuffed length and flags
+    size_t stream;      // n * sstride: the scan without its stuffed zeros, 8 spare bytes behind
+    size_t chunk_sums;  // n * chunks u32: stuffed zeros per 1024 bytes of scan, then their exclusive scan
+    size_t chunk_offs;
+    size_t entries;     // n * seqs * kJpeghSeq u64: entry state per subsequence
+    size_t counts;      // n * seqs * kJpeghSeq u32: blocks completed per subsequence
+    size_t seq_exit;    // 2 * n * seqs u64: exit state per sequence, of the even and of the odd launches
+    size_t seq_sums;    // n * seqs u32: blocks per sequence, then their exclusive scan
+    size_t seq_offs;
+    size_t dcdiff;      // n * blocks i32: DC difference per block of the scan
+    size_t dc_sums;     // n * tiles * 3 i32: per tile and component, then their exclusive scan as i64
+    size_t dc_offs;
+    size_t payload;     // n * (384 + cap): MIPX_OP_JPEGD's payloads, when the call goes on to pixels
+    size_t planes;      // n * w * h * 3: MIPX_OP_JPEGD's own workspace
+    size_t total;
+    JpeghWork(int n, int w, int h) {
+        auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+        const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
+        const size_t mcus = ((ywb + 1) / 2) * ((yhb + 1) / 2), N = static_cast<size_t>(n);
+        cap = 384 * ywb * yhb;
+        blocks = 3 * ywb * yhb > 6 * mcus ? 3 * ywb * yhb : 6 * mcus;
+        tiles = (blocks + kJpeghSeq - 1) / kJpeghSeq;
+        chunks = (cap + 4 * kJpeghSeq - 1) / (4 * kJpeghSeq);
+        seqs = (cap + kJpeghSub * kJpeghSeq - 1) / (kJpeghSub * kJpeghSeq);
+        sstride = up(cap + 8);
+        status = 0;
+        info = status + up(N * 4);
+        stream = info + up(N * 32);
+        chunk_sums = stream + N * sstride;
+        chunk_offs = chunk_sums + up(N * chunks * 4);
+        entries = chunk_offs + up(N * chunks * 4);
+        counts = entries + up(N * seqs * kJpeghSeq * 8);
+        seq_exit = counts + up(N * seqs * kJpeghSeq * 4);
+        seq_sums = seq_exit + up(2 * N * seqs * 8);
+        seq_offs = seq_sums + up(N * seqs * 4);
+        dcdiff = seq_offs + up(N * seqs * 4);
+        dc_sums = dcdiff + up(N * blocks * 4);
+        dc_offs = dc_sums + up(N * tiles * 12);
+        payload = dc_offs + up(N * tiles * 24);
+        planes = payload + up(N * (384 + cap));
+        total = planes + up(N * static_cast<size_t>(w) * h * 3);
+    }
+};
 // k_smartcrop.hip
 size_t smartcrop_workspace_bytes(int n, int w, int h, int bands);
 int smartcrop_origins(const uint8_t *in, int *origins, int n, int w, int h, int b, int cw, int ch, void *ws,
@@ -260,8 +317,9 @@ int smartcrop_extract(const uint8_t *in, uint8_t *out, int n, int w, int h, int 
 size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, double p1);
 
 // mipx_planner.cpp: bytes per image of the plan's input buffer: w * h * bands, or the packed
-// planes when step 0 is MIPX_OP_YCC, the coefficient payload when it is MIPX_OP_JPEGD (header
-// fields already validated): of the file's size, which a scaled step carries in a[2], a[3]
+// planes when step 0 is MIPX_OP_YCC, the coefficient payload when it is MIPX_OP_JPEGD, the scan's
+// slot when it is MIPX_OP_JPEGH (header fields already validated): of the file's size, which a
+// scaled step carries in a[2], a[3]
 size_t plan_input_bytes(const mipx_plan *p);
 // bytes per image of the plan's output buffer: out_w * out_h * out_bands, or the coefficients
 // when the last step is MIPX_OP_JPEGC, or the scan's slot when it is MIPX_OP_JPEGE (plan already validated)

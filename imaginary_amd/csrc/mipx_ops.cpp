@@ -33,6 +33,9 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
         // the entropy coder's: the coefficients, the scan before stuffing, the per-block and
         // per-tile bit counts and their scans (JpegeWork); sized without the layout
         case MIPX_OP_JPEGE: return JpegeWork(n, w, h).total;
+        // the entropy decoder's: the unstuffed scans, the decoders' states and block counts, the DC
+        // differences, and what the coefficient step behind it needs (JpeghWork); sized without the layout
+        case MIPX_OP_JPEGH: return JpeghWork(n, w, h).total;
         default: return 0;
     }
 }
@@ -199,6 +202,55 @@ int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int
     const int e = jpegc_launch(d_in, coefs, n, w, h, layout, quality, as_stream(stream));
     if (e) return e;
     return jpege_launch(coefs, d_out, n, w, h, layout, work, as_stream(stream));
+}
+
+// The checks the three entropy-decoder calls share; *work: the workspace.
+static int jpegh_check(const char *what, const void *d_slots, const void *d_out, const uint32_t *d_status, int32_t n,
+                       int32_t w, int32_t h, int32_t layout, void *d_ws, size_t ws_bytes) {
+    if (!d_slots || !d_out || !d_status || !d_ws || !geom_ok(n, w, h, 3) ||
+        (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
+        return MIPX_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 15u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
+        set_error("%s: the workspace is not 16-byte aligned, or the statuses are not 4-byte aligned", what);
+        return MIPX_EINVAL;
+    }
+    // bit offsets inside a scan are 32-bit in the kernels
+    if (mipx_jpegc_bytes(w, h, layout) >= (1ull << 29) || 3ull * w * h > 0xffffffffull) {
+        set_error("%s: image %dx%d too large (a scan of 2^32 bits or more)", what, w, h);
+        return MIPX_EUNSUPPORTED;
+    }
+    if (ws_bytes < op_workspace_bytes(MIPX_OP_JPEGH, n, w, h, 3, 0, 0)) {
+        set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, op_workspace_bytes(MIPX_OP_JPEGH, n, w, h, 3, 0, 0));
+        return MIPX_EINVAL;
+    }
+    return MIPX_OK;
+}
+
+int mipx_op_jpegh_to_jpegd(const uint8_t *d_slots, uint8_t *d_payloads, uint32_t *d_status, int32_t n, int32_t w,
+                           int32_t h, int32_t layout, void *d_ws, size_t ws_bytes, void *stream) {
+    const int e = jpegh_check("jpeg scan to coefficients", d_slots, d_payloads, d_status, n, w, h, layout, d_ws, ws_bytes);
+    if (e) return e;
+    return jpegh_launch(d_slots, d_payloads, d_status, n, w, h, layout, static_cast<uint8_t *>(d_ws), as_stream(stream));
+}
+
+int mipx_op_jpegh_to_rgb_scaled(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_status, int32_t n, int32_t file_w,
+                                int32_t file_h, int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes,
+                                void *stream) {
+    if (shrink == 0) shrink = 1;
+    if (shrink != 1 && shrink != 2 && shrink != 4 && shrink != 8) return MIPX_EINVAL;
+    int e = jpegh_check("jpeg scan to rgb", d_slots, d_out, d_status, n, file_w, file_h, layout, d_ws, ws_bytes);
+    if (e) return e;
+    const JpeghWork W(n, file_w, file_h);
+    uint8_t *work = static_cast<uint8_t *>(d_ws);
+    e = jpegh_launch(d_slots, work + W.payload, d_status, n, file_w, file_h, layout, work, as_stream(stream));
+    if (e) return e;
+    return mipx_op_jpegd_to_rgb_scaled(work + W.payload, d_out, n, file_w, file_h, layout, shrink, work + W.planes,
+                                       W.total - W.planes, stream);
+}
+
+int mipx_op_jpegh_to_rgb(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_status, int32_t n, int32_t w, int32_t h,
+                         int32_t layout, void *d_ws, size_t ws_bytes, void *stream) {
+    return mipx_op_jpegh_to_rgb_scaled(d_slots, d_out, d_status, n, w, h, layout, 1, d_ws, ws_bytes, stream);
 }
 
 int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,

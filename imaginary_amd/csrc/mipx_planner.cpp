@@ -626,6 +626,11 @@ size_t mipx::plan_input_bytes(const mipx_plan *p) {
         if (s.a[1] > 1) return mipx_jpegd_bytes(s.a[2], s.a[3], s.a[0]);
         return mipx_jpegd_bytes(p->in_w, p->in_h, s.a[0]);
     }
+    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_JPEGH) {  // the same rule for the scan's slot
+        const mipx_step &s = p->steps[0];
+        if (s.a[1] > 1) return mipx_jpegh_bytes(s.a[2], s.a[3], s.a[0]);
+        return mipx_jpegh_bytes(p->in_w, p->in_h, s.a[0]);
+    }
     return static_cast<size_t>(p->in_w) * p->in_h * p->in_bands;
 }
 
@@ -639,8 +644,8 @@ extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
         mipx::set_error("mipx_plan_set_ycc_input: the plan already takes planar input");
         return MIPX_EINVAL;
     }
-    if (plan->n_steps > 0 && plan->steps[0].op == MIPX_OP_JPEGD) {
-        mipx::set_error("mipx_plan_set_ycc_input: the plan already takes coefficient input");
+    if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_JPEGD || plan->steps[0].op == MIPX_OP_JPEGH)) {
+        mipx::set_error("mipx_plan_set_ycc_input: the plan already takes coefficient or scan input");
         return MIPX_EINVAL;
     }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
@@ -669,6 +674,11 @@ extern "C" size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout) {
 extern "C" size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout) {
     const size_t coefs = mipx_jpegc_bytes(w, h, layout);
     return coefs ? MIPX_JPEG_SCAN_HEADER_BYTES + coefs : 0;
+}
+
+extern "C" size_t mipx_jpegh_bytes(int32_t w, int32_t h, int32_t layout) {
+    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
+    return coefs ? MIPX_JPEGH_HEADER_BYTES + coefs : 0;
 }
 
 // whether the plan's last step makes its output something else than pixels
@@ -792,17 +802,21 @@ extern "C" size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout) {
     return coefs ? MIPX_JPEGD_HEADER_BYTES + coefs : 0;
 }
 
-// shrink 1: the full-size step; 2, 4, 8: the step that decodes the file_w x file_h file at that scale
+// shrink 1: the full-size step; 2, 4, 8: the step that decodes the file_w x file_h file at that scale.
+// op: MIPX_OP_JPEGD, or MIPX_OP_JPEGH for the same step behind the entropy decoder
 static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w, int32_t file_h,
-                           const char *who) {
+                           const char *who, int32_t op = MIPX_OP_JPEGD) {
     if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
     if (plan->in_bands != 3) {
         mipx::set_error("%s: the plan takes %d bands, a YCbCr JPEG makes 3", who, plan->in_bands);
         return MIPX_EINVAL;
     }
-    if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_YCC || plan->steps[0].op == MIPX_OP_JPEGD)) {
+    if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_YCC || plan->steps[0].op == MIPX_OP_JPEGD ||
+                              plan->steps[0].op == MIPX_OP_JPEGH)) {
         mipx::set_error("%s: the plan already takes %s input", who,
-                        plan->steps[0].op == MIPX_OP_YCC ? "planar" : "coefficient");
+                        plan->steps[0].op == MIPX_OP_YCC     ? "planar"
+                        : plan->steps[0].op == MIPX_OP_JPEGD ? "coefficient"
+                                                             : "scan");
         return MIPX_EINVAL;
     }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
@@ -829,7 +843,7 @@ static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int3
     ++plan->n_steps;
     mipx_step &s = plan->steps[0];
     std::memset(&s, 0, sizeof(s));
-    s.op = MIPX_OP_JPEGD;
+    s.op = op;
     s.a[0] = layout;
     if (shrink != 1) s.a[1] = shrink, s.a[2] = file_w, s.a[3] = file_h;
     s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = 3;
@@ -844,6 +858,17 @@ extern "C" int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout) {
 extern "C" int mipx_plan_set_jpegd_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
                                                 int32_t file_h) {
     return set_jpegd_input(plan, layout, shrink, file_w, file_h, "mipx_plan_set_jpegd_input_scaled");
+}
+
+// ---- entropy-coded JPEG input (MIPX_OP_JPEGH) ---------------------------------------
+extern "C" int mipx_plan_set_jpegh_input(mipx_plan *plan, int32_t layout) {
+    if (!plan) return MIPX_EINVAL;
+    return set_jpegd_input(plan, layout, 1, plan->in_w, plan->in_h, "mipx_plan_set_jpegh_input", MIPX_OP_JPEGH);
+}
+
+extern "C" int mipx_plan_set_jpegh_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
+                                                int32_t file_h) {
+    return set_jpegd_input(plan, layout, shrink, file_w, file_h, "mipx_plan_set_jpegh_input_scaled", MIPX_OP_JPEGH);
 }
 
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {
@@ -873,6 +898,10 @@ extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_p
             }
             if (k > 0 && s.steps[i].op == MIPX_OP_JPEGD) {  // ... or a file's coefficients
                 mipx::set_error("mipx_plan_chain: stage %d takes coefficient input; only stage 0 may", k);
+                return MIPX_EINVAL;
+            }
+            if (k > 0 && s.steps[i].op == MIPX_OP_JPEGH) {  // ... or a file's scan
+                mipx::set_error("mipx_plan_chain: stage %d takes scan input; only stage 0 may", k);
                 return MIPX_EINVAL;
             }
             if (k + 1 < n_stages && s.steps[i].op == MIPX_OP_JPEGC) {  // only the request's output can be coefficients

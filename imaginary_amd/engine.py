@@ -11,8 +11,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, YCC_444, YCC_420,
-                   JPEG_SCAN_HEADER_BYTES, sync_tuning)
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, OP_JPEGH, YCC_444, YCC_420,
+                   JPEG_SCAN_HEADER_BYTES, JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
@@ -21,6 +21,7 @@ __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
            "plan_set_jpeg_scan_output", "jpeg_scan_bytes", "rgb_to_jpeg_scan", "jpegc_to_scan", "scan_slot",
+           "jpegh_bytes", "plan_set_jpegh_input", "plan_set_jpegh_input_scaled", "execute_status", "jpegh_to_jpegd", "jpegh_to_rgb", "jpegh_to_rgb_scaled", "JPEGH_OK", "JPEGH_UNSYNCED", "JPEGH_BAD",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
 
@@ -300,9 +301,14 @@ def _jpegd_file_size(plan: MipxPlan):
     return (a[2], a[3]) if a[1] > 1 else (plan.in_w, plan.in_h)
 
 
+def _jpegh_layout(plan: MipxPlan):
+    """The layout of the entropy-coded slot a plan's input is, or None for anything else."""
+    return plan.steps[0].a[0] if plan.n_steps > 0 and plan.steps[0].op == OP_JPEGH else None
+
+
 def _packed_input(plan: MipxPlan) -> bool:
-    """Whether the plan's input is bytes per image (planes or a coefficient payload), not pixels."""
-    return _ycc_layout(plan) is not None or _jpegd_layout(plan) is not None
+    """Whether the plan's input is bytes per image (planes, a coefficient payload or a scan's slot), not pixels."""
+    return _ycc_layout(plan) is not None or _jpegd_layout(plan) is not None or _jpegh_layout(plan) is not None
 
 
 def _planes(plan: MipxPlan, planes) -> np.ndarray:
@@ -312,6 +318,8 @@ def _planes(plan: MipxPlan, planes) -> np.ndarray:
         x = x[None]
     if _jpegd_layout(plan) is not None:
         need, what = jpegd_bytes(*_jpegd_file_size(plan), _jpegd_layout(plan)), "coefficient"
+    elif _jpegh_layout(plan) is not None:
+        need, what = jpegh_bytes(*_jpegd_file_size(plan), _jpegh_layout(plan)), "scan"
     else:
         need, what = ycc_bytes(plan.in_w, plan.in_h, _ycc_layout(plan)), "planar"
     if x.ndim != 2 or x.shape[1] != need:
@@ -340,6 +348,21 @@ def plan_set_jpegd_input_scaled(plan: MipxPlan, layout: int, shrink: int, file_w
     shrink-on-load does.  shrink 1 is plan_set_jpegd_input."""
     check(lib.mipx_plan_set_jpegd_input_scaled(C.byref(plan), layout, shrink, file_w, file_h),
           "mipx_plan_set_jpegd_input_scaled")
+    return plan
+
+
+def plan_set_jpegh_input(plan: MipxPlan, layout: int) -> MipxPlan:
+    """mipx_plan_set_jpegh_input on `plan` (in place; returned for convenience): the plan then
+    takes a JPEG's tables and entropy-coded scan (codec.jpeg_huff_slot; YCC_444 or YCC_420)
+    instead of RGB pixels."""
+    check(lib.mipx_plan_set_jpegh_input(C.byref(plan), layout), "mipx_plan_set_jpegh_input")
+    return plan
+
+
+def plan_set_jpegh_input_scaled(plan: MipxPlan, layout: int, shrink: int, file_w: int, file_h: int) -> MipxPlan:
+    """mipx_plan_set_jpegh_input_scaled: as plan_set_jpegd_input_scaled, on the file's slot."""
+    check(lib.mipx_plan_set_jpegh_input_scaled(C.byref(plan), layout, shrink, file_w, file_h),
+          "mipx_plan_set_jpegh_input_scaled")
     return plan
 
 
@@ -743,6 +766,70 @@ def jpegd_to_rgb_scaled(payload: np.ndarray, w: int, h: int, layout: int, shrink
     return dout.download((n, oh, ow, 3))
 
 
+def jpegh_bytes(w: int, h: int, layout: int) -> int:
+    """mipx_jpegh_bytes: bytes of one image's entropy-coded input slot, the 1504 bytes of header and
+    tables and jpegc_bytes of room for the scan (0 for bad arguments)."""
+    return int(lib.mipx_jpegh_bytes(w, h, layout))
+
+
+def _jpegh_slots(slots, w: int, h: int, layout: int) -> np.ndarray:
+    x = np.ascontiguousarray(slots, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x[None]
+    need = jpegh_bytes(w, h, layout)
+    if x.ndim != 2 or need == 0 or x.shape[1] != need:
+        raise ValueError(f"slots of shape {np.shape(slots)} for {w}x{h} layout {layout}: {need} bytes per image")
+    return x
+
+
+def jpegh_to_jpegd(slots: np.ndarray, w: int, h: int, layout: int):
+    """mipx_op_jpegh_to_jpegd on entropy-coded input slots (codec.jpeg_huff_slot), (bytes,) or
+    (n, bytes) uint8; returns (payloads, status): (n, jpegd_bytes) uint8 as codec.decode_jpeg_coefs
+    gives them, and (n,) uint32 of JPEGH_OK / JPEGH_UNSYNCED / JPEGH_BAD."""
+    sync_tuning()
+    x = _jpegh_slots(slots, w, h, layout)
+    n, need = x.shape[0], jpegd_bytes(w, h, layout)
+    what = "mipx_op_jpegh_to_jpegd"
+    din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
+    dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
+    dst = _dev("status", what, 4 * n)
+    wsb = lib.mipx_op_workspace_bytes(OP_JPEGH, n, w, h, 3, 0.0, 0.0)
+    ws = _dev("ws", what, wsb)
+    check(lib.mipx_op_jpegh_to_jpegd(din.ptr, dout.ptr, dst.ptr, n, w, h, layout, ws.ptr, wsb, None), what)
+    synchronize()
+    _check_guards(what, din, dout, dst, ws)
+    return dout.download((n, need)), dst.download((n,), np.uint32)
+
+
+def jpegh_to_rgb_scaled(slots: np.ndarray, w: int, h: int, layout: int, shrink: int, _full: bool = False):
+    """mipx_op_jpegh_to_rgb_scaled on the entropy-coded input slots of w x h files; returns
+    (pixels, status): (n, ceil(h / shrink), ceil(w / shrink), 3) uint8, unspecified where the
+    status is not JPEGH_OK, and (n,) uint32."""
+    sync_tuning()
+    x = _jpegh_slots(slots, w, h, layout)
+    if shrink not in (1, 2, 4, 8):
+        raise ValueError(f"shrink {shrink}: 1, 2, 4 or 8")
+    n, ow, oh = x.shape[0], -(-w // shrink), -(-h // shrink)
+    what = "mipx_op_jpegh_to_rgb" if _full else "mipx_op_jpegh_to_rgb_scaled"
+    din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
+    dout = _dev("out", what, n * oh * ow * 3, ow * 3)
+    dst = _dev("status", what, 4 * n)
+    wsb = lib.mipx_op_workspace_bytes(OP_JPEGH, n, w, h, 3, 0.0, 0.0)
+    ws = _dev("ws", what, wsb)
+    if _full:
+        check(lib.mipx_op_jpegh_to_rgb(din.ptr, dout.ptr, dst.ptr, n, w, h, layout, ws.ptr, wsb, None), what)
+    else:
+        check(lib.mipx_op_jpegh_to_rgb_scaled(din.ptr, dout.ptr, dst.ptr, n, w, h, layout, shrink, ws.ptr, wsb, None), what)
+    synchronize()
+    _check_guards(what, din, dout, dst, ws)
+    return dout.download((n, oh, ow, 3)), dst.download((n,), np.uint32)
+
+
+def jpegh_to_rgb(slots: np.ndarray, w: int, h: int, layout: int):
+    """mipx_op_jpegh_to_rgb: as jpegh_to_rgb_scaled, at full size."""
+    return jpegh_to_rgb_scaled(slots, w, h, layout, 1, _full=True)
+
+
 def jpeg_roundtrip(imgs: np.ndarray, layout: int, quality: int, shrink: int = 1) -> np.ndarray:
     """mipx_op_jpeg_roundtrip on (h, w, 3) or (n, h, w, 3) uint8: the pixels the JPEG of each image
     at `quality` decodes to at 1/shrink; returns (n, ceil(h / shrink), ceil(w / shrink), 3)."""
@@ -814,11 +901,22 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
                                ws.ptr if ws else None, wsb, None), what)
     synchronize()
     _check_guards(what, din, dout, dwm, ws)
+    global _last_status
+    _last_status = ws.download((n,), np.uint32) if _jpegh_layout(plan) is not None else None
     if coefs is not None:
         return dout.download((n, out1 // 2), np.int16)
     if scan is not None:
         return dout.download((n, out1))
     return dout.download((n, plan.out_h, plan.out_w, plan.out_bands))
+
+
+_last_status = None
+
+
+def execute_status():
+    """The statuses (n uint32 of JPEGH_*) the last execute() of a plan with entropy-coded input
+    (plan_set_jpegh_input[_scaled]) left at the head of its workspace; None after any other plan."""
+    return _last_status
 
 
 def _wm_row_bytes(wm: np.ndarray) -> int:

@@ -30,7 +30,7 @@ import numpy as np
 from . import _abi, codec
 from .engine import (Engine, fit_dimension, make_input, make_opts, plan_add_jpeg_roundtrip, plan_add_textmark,
                      plan_chain, plan_make, plan_set_jpeg_scan_output, plan_set_jpegc_output, plan_set_jpegd_input,
-                     plan_set_jpegd_input_scaled, plan_set_ycc_input, plan_textmark_geometry, scan_slot)
+                     plan_set_jpegd_input_scaled, plan_set_jpegh_input, plan_set_jpegh_input_scaled, plan_set_ycc_input, plan_textmark_geometry, scan_slot)
 
 HTTP_BAD_REQUEST = 400
 HTTP_NOT_ACCEPTABLE = 406
@@ -50,6 +50,14 @@ class EngineUnsupported(ImaginaryError):
 
     def __init__(self, message: str):
         super().__init__(message, 501)
+
+
+class ScanNotDecodable(ImaginaryError):
+    """The engine could not entropy-decode a request's JPEG scan (MIPX_EDATA): the caller decodes
+    it on the host and runs the request again."""
+
+    def __init__(self, message: str):
+        super().__init__(message, 500)
 
 
 @dataclass
@@ -444,6 +452,8 @@ def _run(plan, px, wm):
     except _abi.MipxError as e:
         if e.code == _abi.MIPX_EUNSUPPORTED:
             raise EngineUnsupported(str(e)) from e
+        if e.code == _abi.MIPX_EDATA:
+            raise ScanNotDecodable(str(e)) from e
         raise ImaginaryError(f"image processing error: {e}", 500) from e
 
 
@@ -504,7 +514,8 @@ class JpegScan:
 
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
             text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None,
-            jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False, jpeg_scan: bool = False):
+            jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False, jpeg_scan: bool = False,
+            jpeg_huff: Optional[tuple] = None):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -524,6 +535,11 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     also takes them: the engine decodes the full-size file's payload at the scale the host codec
     would deliver (codec.decode_scale), as libjpeg's shrink-on-load does, and `redecode` is not
     called.
+    With `jpeg_huff` = (slot, layout) (codec.jpeg_huff_slot) in the place of `jpeg_dct`, the plan
+    takes the file's entropy-coded scan and the engine runs the Huffman decoder too, at full size
+    and with `jpeg_dct_shrink` at the shrink-on-load scales; it takes precedence over `jpeg_dct`.
+    A scan the engine reports as not decodable raises ScanNotDecodable: run the request again
+    with `jpeg_dct`.
     With `jpeg_quality` (1..100) and a 3-band result, the plan ends with the coefficient step
     (4:2:0 below Q 90, 4:4:4 from Q 90, as codec.encode samples) and a JpegCoefs is returned;
     results of other band counts come back as pixels.  With `jpeg_scan` too, the plan ends with the
@@ -540,6 +556,9 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
         wm = wm if wm.ndim == 3 else wm[:, :, None]
         opts = dict(opts, wm_enable=1)
         inp.wm_w, inp.wm_h, inp.wm_bands = wm.shape[1], wm.shape[0], wm.shape[2]
+    huff = jpeg_huff is not None
+    if huff:
+        jpeg_dct = jpeg_huff   # the same requests, the same plans, another step 0
     try:
         plan = plan_make(make_opts(**opts), inp)
         dct_scale = None   # the scale the engine decodes the coefficients at, when it shrinks on load
@@ -558,12 +577,12 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
         if text is not None:
             wm = _add_textmark(plan, text)
         if jpeg_dct is not None and dct_scale is not None:
-            plan_set_jpegd_input_scaled(plan, jpeg_dct[1], dct_scale, img.w, img.h)
+            (plan_set_jpegh_input_scaled if huff else plan_set_jpegd_input_scaled)(plan, jpeg_dct[1], dct_scale, img.w, img.h)
             px = jpeg_dct[0]
         elif jpeg_dct is not None:
             if plan.load_shrink > 1 or chain is not None:
                 raise ImaginaryError("coefficient input needs the full-size decode of a single request", 500)
-            plan_set_jpegd_input(plan, jpeg_dct[1])
+            (plan_set_jpegh_input if huff else plan_set_jpegd_input)(plan, jpeg_dct[1])
             px = jpeg_dct[0]
         elif ycc is not None:
             if plan.load_shrink > 1 or chain is not None:
@@ -593,7 +612,8 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
-                  jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False) -> Image:
+                  jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False,
+                  jpeg_huff: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -615,6 +635,11 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     jpeg_dct_shrink: with jpeg_dct, a shrink-on-load request that does not rotate goes to the engine as
     coefficients too, decoded there at the scale codec.decode(buf, shrink) would deliver; the bytes
     are the same either way.
+    jpeg_huff: hand such a JPEG to the engine as its entropy-coded scan (codec.jpeg_huff_slot), so the
+    host only reads markers and the upload is the file's size; tried before jpeg_dct, on the requests
+    jpeg_dct takes (with jpeg_dct_shrink, on the shrink-on-load ones too).  A file jpeg_huff_slot
+    declines (restart intervals, more than two tables of a kind) and a scan the engine reports as not
+    decodable (MIPX_EDATA) go on as jpeg_dct does; the bytes are the same either way.
     device_reencode: a 3-band JPEG that rotates and shrinks on load (_rotate_reencode_shrink_on_load)
     runs as one plan, the re-encode and the scaled decode as a MIPX_OP_JPEGRT step between the
     rotation and the rest: one upload, no host codec in between; the bytes are the same either way."""
@@ -651,15 +676,28 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     if plan.load_shrink > 1 and itype == "jpeg" and rotates and not opts.get("no_auto_rotate"):
         px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text, device=device_reencode)
     elif plan.load_shrink > 1:  # process() re-plans on the codec-shrunk size
-        take = jpeg_dct and jpeg_dct_shrink and hdr.bands == 3 and itype == "jpeg" and not rotates
-        dct = codec.decode_jpeg_coefs(buf) if take else None
+        take = (jpeg_dct or jpeg_huff) and jpeg_dct_shrink and hdr.bands == 3 and itype == "jpeg" and not rotates
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
-        px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
-                     jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan)
+        px = None
+        if take and jpeg_huff:
+            px = _with_scan(buf, lambda slot: process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq,
+                                                      jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan))
+        if px is None:
+            dct = codec.decode_jpeg_coefs(buf) if take else None
+            px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
+                         jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan)
     else:
-        dct = codec.decode_jpeg_coefs(buf) if jpeg_dct and hdr.bands == 3 and itype == "jpeg" else None
-        planes = codec.decode_ycc(buf) if dct is None and ycc and hdr.bands == 3 else None
-        if dct is not None:
+        take = (jpeg_dct or jpeg_huff) and hdr.bands == 3 and itype == "jpeg"
+        px = None
+        if take and jpeg_huff:
+            px = _with_scan(buf, lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts,
+                                                      wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq,
+                                                      jpeg_scan=jpeg_scan))
+        dct = codec.decode_jpeg_coefs(buf) if take and px is None else None
+        planes = codec.decode_ycc(buf) if px is None and dct is None and ycc and hdr.bands == 3 else None
+        if px is not None:
+            pass
+        elif dct is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
                          jpeg_dct=dct, jpeg_quality=jq, jpeg_scan=jpeg_scan)
         elif planes is not None:
@@ -675,6 +713,18 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)
         return Image(body, codec.mime_type(codec.sniff_type(body)))
     return _encode(px, t, quality, compression)
+
+
+def _with_scan(buf: bytes, run):
+    """run((slot, layout)) of the file's entropy-coded scan; None where the file has no slot
+    (codec.jpeg_huff_slot) or the engine could not decode it, and the caller goes on without."""
+    slot = codec.jpeg_huff_slot(buf)
+    if slot is None:
+        return None
+    try:
+        return run(slot)
+    except ScanNotDecodable:
+        return None
 
 
 def _encode(px: np.ndarray, t: str, quality: int, compression) -> Image:

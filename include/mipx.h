@@ -44,6 +44,9 @@
  *    n * mipx_jpeg_scan_bytes() output bytes instead (entropy-coded scans), at any alignment.
  *    A plan that starts with MIPX_OP_JPEGD, and mipx_op_jpegd_to_rgb, read n * mipx_jpegd_bytes()
  *    input bytes instead (quantisation tables + JPEG coefficients), at any alignment.
+ *    A plan that starts with MIPX_OP_JPEGH, and mipx_op_jpegh_to_*, read n slots of
+ *    mipx_jpegh_bytes() instead (tables + a JPEG's entropy-coded scan), at any alignment, and of
+ *    each slot only the header and the scan's `length` bytes.
  *  - Thread-safe: mipx_submit / mipx_wait / mipx_process may be called from
  *    many threads (one goroutine per HTTP request).
  */
@@ -70,6 +73,7 @@ extern "C" {
 #define MIPX_ENOTINIT (-7)
 #define MIPX_ESTALE (-8)         /* unknown or already-waited ticket */
 #define MIPX_EBUSY (-9)          /* refused while requests are queued or running */
+#define MIPX_EDATA (-10)         /* input not decodable on the device (MIPX_OP_JPEGH: status not MIPX_JPEGH_OK) */
 
 /* ---- bimg enums (bimg v1.1.9 options.go / type.go) ---- */
 enum { MIPX_GRAVITY_CENTRE = 0, MIPX_GRAVITY_NORTH, MIPX_GRAVITY_EAST, MIPX_GRAVITY_SOUTH,
@@ -157,11 +161,16 @@ enum {
                             ceil(w / shrink) x ceil(h / shrink) x 3: the pixels the JPEG of the image at that
                             quality decodes to at that scale (mipx_plan_add_jpeg_roundtrip)
                                   (MIPX_OP_JPEGC's rule, then MIPX_OP_JPEGD's with the same tables) */
-    MIPX_OP_JPEGE        /* = 19, the entropy-coded scan: a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/
+    MIPX_OP_JPEGE,       /* = 19, the entropy-coded scan: a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/
                             out_bands = the image it consumes (w, h, 3); only as the LAST step of a plan whose
                             image there has 3 bands, never together with MIPX_OP_JPEGC; the output buffer is
                             then one slot per image (mipx_plan_set_jpeg_scan_output)
                                   (MIPX_OP_JPEGC's rule, then libjpeg's baseline Huffman coder) */
+    MIPX_OP_JPEGH        /* = 20, entropy-coded JPEG input (see MIPX_JPEGH_HEADER_BYTES): a[] exactly as
+                            MIPX_OP_JPEGD (layout; shrink 0 or 1, or 2, 4, 8 with the file's size in a[2], a[3]);
+                            only as step 0, never beside MIPX_OP_YCC or MIPX_OP_JPEGD, in a chain in stage 0
+                            only; the input buffer is then one slot per image (mipx_plan_set_jpegh_input)
+                                  (libjpeg's baseline Huffman decoder, then MIPX_OP_JPEGD's rule) */
 };
 
 /* Planar YCbCr input, as a JPEG decoder has it before its upsample and colour conversion
@@ -236,6 +245,33 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
 #define MIPX_JPEG_SCAN_HEADER_BYTES 16
 enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODABLE = 2 };
 #define MIPX_JPEGD_HEADER_BYTES 384
+/* Entropy-coded JPEG input (mipx_op_jpegh_*): the file's scan bytes instead of its coefficients, a
+ * fifth to a third of their size, so the host only reads markers.  The engine decodes a baseline
+ * (or extended sequential) Huffman scan of three components, one interleaved scan without restart
+ * markers, into exactly MIPX_OP_JPEGD's payload (PARITY_ASSUMPTIONS.md row 22).
+ *    One image's input is a slot of mipx_jpegh_bytes(w, h, layout) = MIPX_JPEGH_HEADER_BYTES +
+ * mipx_jpegc_bytes(w, h, layout) bytes, all fields little-endian, starting on any byte:
+ *      0  uint32 length: bytes of entropy-coded data behind the header, exactly as in the file
+ *         between the SOS segment and FF D9 (stuffed); then three uint32 zeros
+ *     16  384 bytes: the quantisation tables of Y, Cb, Cr, as in MIPX_OP_JPEGD's payload
+ *    400  6 bytes: DC table index of Y, Cb, Cr, then AC table index of Y, Cb, Cr (0 or 1); 10 zeros
+ *    416  four tables of 272 bytes, DC 0, DC 1, AC 0, AC 1: the DHT's 16 counts, then up to 256
+ *         symbols, zero-padded; a table the file does not define is all zero
+ *   1504  the scan
+ * Bytes of the slot past `length` are never read.  Per image a status comes back:
+ * MIPX_JPEGH_OK: the payload holds what jpeg_read_coefficients gives for the file.
+ * MIPX_JPEGH_UNSYNCED: the decoders, started at every 128th byte of the unstuffed scan, did not
+ * agree on the codeword boundaries within the fixed number of launches (scans of more than 64
+ * KiB almost without end-of-block codes); the caller decodes on the host instead.
+ * MIPX_JPEGH_BAD: not decodable: length above the capacity; an FF that no 00 follows (a marker, a
+ * restart marker, a fill byte, the last byte); code counts that sum past 256 or overflow a length;
+ * a table index above 1; a code that is in no table; a run and value that pass coefficient 63; a
+ * DC symbol above 15; a scan that ends before its last block; a DC outside int16.  (A run of 16
+ * zeros that passes coefficient 63 ends the block, as in libjpeg.)  Bits behind the last block are
+ * ignored.  The payload of an image whose status is not OK is unspecified, but every write stays
+ * inside it. */
+#define MIPX_JPEGH_HEADER_BYTES 1504
+enum { MIPX_JPEGH_OK = 0, MIPX_JPEGH_UNSYNCED = 1, MIPX_JPEGH_BAD = 2 };
 
 #define MIPX_MAX_STEPS 64   /* room for a merged /pipeline chain (mipx_plan_chain) */
 typedef struct mipx_step {
@@ -487,6 +523,43 @@ int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int
                           int32_t layout, void *d_work, void *stream);
 int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                              int32_t layout, int32_t quality, void *d_work, void *stream);
+/* The entropy decoder (see MIPX_JPEGH_HEADER_BYTES): n slots (n * mipx_jpegh_bytes(w, h, layout)
+ * bytes) -> n payloads of MIPX_OP_JPEGD (n * mipx_jpegd_bytes(w, h, layout) bytes) and n uint32
+ * statuses (MIPX_JPEGH_*).  mipx_jpegh_bytes works without a GPU: MIPX_JPEGH_HEADER_BYTES +
+ * mipx_jpegc_bytes(w, h, layout), 0 where that is 0.  Slots, payloads and pixels at any alignment;
+ * d_status 4-byte aligned; d_ws 16-byte aligned device memory of at least
+ * mipx_op_workspace_bytes(MIPX_OP_JPEGH, n, w, h, 3, 0, 0) bytes (one size for the three calls and
+ * both layouts: the unstuffed scans, the decoders' states, the DC differences, and for the calls
+ * that go on to pixels the payloads and MIPX_OP_JPEGD's planes; w, h the file's size).
+ * mipx_op_jpegh_to_rgb[_scaled] run the decoder and then mipx_op_jpegd_to_rgb[_scaled]; the pixels
+ * of an image whose status is not OK are unspecified, the other images are unaffected.  A call is
+ * three memsets and 11 launches (13 to pixels); every dependency between workgroups is a launch
+ * boundary, nothing is read back.  MIPX_EINVAL, before any HIP call, for NULL pointers, n <= 0, a
+ * non-positive size, an unknown layout or shrink, a misaligned or short workspace, a misaligned
+ * d_status; MIPX_EUNSUPPORTED for an image whose coefficients are 2^29 bytes or more (bit offsets
+ * are 32-bit) or whose RGB is 2^32 bytes or more. */
+size_t mipx_jpegh_bytes(int32_t w, int32_t h, int32_t layout);
+/* Entropy-coded JPEG input of a plan (MIPX_OP_JPEGH).  Both calls work without a GPU; they are
+ * mipx_plan_set_jpegd_input[_scaled] with the slot in the payload's place: the same composition
+ * rules and MIPX_EINVAL cases, and the four calls (and mipx_plan_set_ycc_input) refuse a plan that
+ * one of them already changed.  The input buffer is mipx_jpegh_bytes(file_w, file_h, layout) bytes
+ * per image.  mipx_execute_dev leaves the n statuses (uint32, MIPX_JPEGH_*) in the first 4 n
+ * bytes of its workspace; the pixels of an image whose status is not MIPX_JPEGH_OK are
+ * unspecified, the other images of the batch are unaffected.  mipx_submit takes a mipx_img of
+ * w = in_w, h = in_h, bands = 3, stride = 0 whose data is the slot; it reads `length` on the host
+ * (above the capacity: MIPX_EINVAL), stages and uploads only the header and `length` bytes, and
+ * counts only those as the queue's pending bytes.  A request whose status is not MIPX_JPEGH_OK
+ * completes with MIPX_EDATA from mipx_wait / mipx_process, its output is not written, and its
+ * batch neighbours complete normally. */
+int mipx_plan_set_jpegh_input(mipx_plan *plan, int32_t layout);
+int mipx_plan_set_jpegh_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w, int32_t file_h);
+int mipx_op_jpegh_to_jpegd(const uint8_t *d_slots, uint8_t *d_payloads, uint32_t *d_status, int32_t n, int32_t w,
+                           int32_t h, int32_t layout, void *d_ws, size_t ws_bytes, void *stream);
+int mipx_op_jpegh_to_rgb(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_status, int32_t n, int32_t w, int32_t h,
+                         int32_t layout, void *d_ws, size_t ws_bytes, void *stream);
+int mipx_op_jpegh_to_rgb_scaled(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_status, int32_t n, int32_t file_w,
+                                int32_t file_h, int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes,
+                                void *stream);
 /* n payloads (n * mipx_jpegd_bytes(w, h, layout) bytes) -> n x h x w x 3 RGB; both pointers at any
  * alignment.  The workspace takes the decoded planes between the two launches (inverse DCT, then
  * the MIPX_OP_YCC kernels): mipx_op_workspace_bytes(MIPX_OP_JPEGD, n, w, h, 3, 0, 0) bytes.

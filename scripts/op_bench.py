@@ -11,9 +11,12 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpegrt420 --w 3840 --h 2160 --n 64 --q 75
     python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75     (RGB -> entropy-coded scan)
     python scripts/op_bench.py jpegcs420 --w 3840 --h 2160 --n 64 --q 75    (the entropy coder alone)
+    python scripts/op_bench.py jpegh420 --w 3840 --h 2160 --n 64 --q 75     (entropy-coded scan -> RGB)
+    python scripts/op_bench.py jpeghd420 --w 3840 --h 2160 --n 64 --q 75    (the entropy decoder alone)
+    python scripts/op_bench.py jpegh420 --file tests/golden/testdata/large.jpg --n 64   (a photograph's scan)
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
          jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444 jpegrt420 jpegrt444
-         jpege420 jpege444 jpegcs420 jpegcs444
+         jpege420 jpege444 jpegcs420 jpegcs444 jpegh420 jpegh444 jpeghd420 jpeghd444
 """
 import argparse
 import ctypes as C
@@ -53,6 +56,8 @@ def main():
     ap.add_argument("--shrink", type=int, default=0, choices=[0, 1, 2, 4, 8],
                     help="jpegds420 / jpegds444: decode the w x h file's coefficients at 1/shrink (0 = 2); "
                          "jpegrt420 / jpegrt444: the round trip's decode at 1/shrink (0 = 1)")
+    ap.add_argument("--file", default="", help="jpegh* / jpeghd*: n copies of this JPEG's scan instead of the coder's "
+                                               "output on noise (sets w, h and the layout)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -123,6 +128,19 @@ def main():
         layout = 1 if a.op.endswith("420") else 0
         in_img = w * h * 3 if a.op.startswith("jpege") else lib.mipx_jpegc_bytes(w, h, layout)
         out_img = lib.mipx_jpeg_scan_bytes(w, h, layout)
+    JPEGH = ("jpegh420", "jpegh444", "jpeghd420", "jpeghd444")
+    file_slot = None
+    if a.op in JPEGH:   # one input slot per image in; RGB (jpegh*) or MIPX_OP_JPEGD's payload (jpeghd*) out
+        b = ob = 3
+        layout = 1 if a.op.endswith("420") else 0
+        if a.file:
+            from imaginary_amd import codec
+            buf = open(a.file, "rb").read()
+            hd = codec.header(buf)
+            file_slot, layout = codec.jpeg_huff_slot(buf)
+            w, h, ow, oh = hd.w, hd.h, hd.w, hd.h
+        in_img = lib.mipx_jpegh_bytes(w, h, layout)
+        out_img = w * h * 3 if a.op.startswith("jpegh4") else lib.mipx_jpegd_bytes(w, h, layout)
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
@@ -130,6 +148,37 @@ def main():
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
     if a.op in JPEGE:
         ws = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
+    if a.op in JPEGH:
+        import numpy as np
+        ws = torch.empty((lib.mipx_op_workspace_bytes(20, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
+        status = torch.zeros((n,), dtype=torch.int32, device=dev)
+        xv = x.view(n, in_img)
+        if file_slot is not None:
+            xv[:] = torch.from_numpy(file_slot).to(dev)
+        else:
+            # what the engine's own coder makes of random pixels at --q, behind that quality's tables and
+            # the Annex K Huffman tables
+            from imaginary_amd import codec
+            lum, chrom = codec.jpeg_qtables(a.q)
+            head = np.zeros(1504, np.uint8)
+            head[16:400] = np.array([lum, chrom, chrom], "<u2").ravel().view(np.uint8)
+            head[400:406] = [0, 1, 1, 0, 1, 1]
+            for i, key in enumerate((0x00, 0x01, 0x10, 0x11)):
+                counts, symbols = codec.HUFFMAN_TABLES[key]
+                head[416 + 272 * i:432 + 272 * i] = list(counts)
+                head[432 + 272 * i:432 + 272 * i + len(symbols)] = list(symbols)
+            px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
+            scans = torch.empty((n, in_img - 1504 + 16), dtype=torch.uint8, device=dev)
+            ews = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            assert lib.mipx_op_rgb_to_jpeg_scan(px.data_ptr(), scans.data_ptr(), n, w, h, layout, a.q, ews.data_ptr(), None) == 0
+            check(lib.mipx_device_sync())
+            assert int(scans[:, 4:8].max()) == 0, "a scan did not fit its slot"
+            xv[:, :1504] = torch.from_numpy(head).to(dev)
+            xv[:, :4] = scans[:, :4]
+            xv[:, 1504:] = scans[:, 16:]
+            del px, scans, ews
+        torch.cuda.synchronize(dev)
     if a.op in ("jpegcs420", "jpegcs444"):
         # the coefficients the engine's own encoder makes of random pixels at --q, as for jpegd*
         px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
@@ -201,6 +250,10 @@ def main():
             return lib.mipx_op_rgb_to_jpeg_scan(X, Y, n, w, h, layout, a.q, WS, sp)
         if a.op in ("jpegcs420", "jpegcs444"):
             return lib.mipx_op_jpegc_to_scan(X, Y, n, w, h, layout, WS, sp)
+        if a.op in ("jpegh420", "jpegh444"):
+            return lib.mipx_op_jpegh_to_rgb(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
+        if a.op in ("jpeghd420", "jpeghd444"):
+            return lib.mipx_op_jpegh_to_jpegd(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
         raise SystemExit(a.op)
 
     # warm-up of >= 200 ms of device time first: a fresh process's first milliseconds run
@@ -239,6 +292,11 @@ def main():
             head = y.view(n, out_img)[:, :16].cpu().numpy().view("<u4")
             line.update(q=a.q, capacity=out_img - 16, mean_length=round(float(head[:, 0].mean()), 1),
                         statuses=sorted(set(head[:, 1].tolist())))
+        if a.op in JPEGH:   # the statuses, and what a request uploads next to its RGB
+            lengths = x.view(n, in_img)[:, :4].cpu().numpy().view("<u4")
+            line.update(q=a.q, file=os.path.basename(a.file), capacity=in_img - 1504,
+                        mean_length=round(float(lengths.mean()), 1), upload_bytes=round(1504 + float(lengths.mean()), 1),
+                        rgb_bytes=w * h * 3, statuses=sorted(set(status.cpu().tolist())))
         print(json.dumps({**line, "ms": round(ms, 4), "alg_GBps": round(alg / ms / 1e6, 1)}))
         return
     # same-process A/B: --ab KNOB=v1,v2,... interleaved over 2 rounds, output checked equal
