@@ -45,8 +45,15 @@ using namespace dev;
 //    13-dword byte window it needs (ds_read_b64: lane stride 6 dwords for RGB,
 //    conflict-free; ds_read_b128 for RGBA, stride 4 dwords), converts each
 //    byte once and stores 12 (RGB) / 8 (RGBA) contiguous output bytes.
-// The intermediate never touches HBM, and the LDS image is 7.5 KB per
-// workgroup, so occupancy is set by registers, not LDS.
+// The intermediate never touches HBM; the 24-row LDS image is 27 KB per workgroup, and
+// both it and the registers (84 VGPRs) allow 5 workgroups per CU.
+// Schedule of a tile (reduce2_onepass, variant 66): one burst of 29 raw loads, one
+// straight-line vertical pass over the band's 24 rows (each consumed register pair
+// refetches the row 12 ahead, every wait is a counted vmcnt), one barrier (two on strips
+// that touch the image edge), one horizontal pass; the kernel ends after its stores.  The
+// chunk-loop body it replaced (reduce2_tile: load, vertical, barrier, horizontal per
+// 12-row chunk, which drains vmcnt to 0 behind the previous chunk's stores) stays as
+// variant 578 for A/B and for MIPX_R2_BAND (profiles/r08/r2_onepass_ab.jsonl).
 // ===========================================================================
 constexpr int kR = 12;           // output rows per LDS chunk (2 ring periods)
 // WIDE level (variant bits 6 / 7): 128 << WIDE threads and strips 2x / 4x as
@@ -125,6 +132,93 @@ __device__ __forceinline__ uint32_t pack4b(float a, float b, float c, float d) {
     v = __builtin_amdgcn_cvt_pk_u8_f32(b, 1, v);
     v = __builtin_amdgcn_cvt_pk_u8_f32(c, 2, v);
     return __builtin_amdgcn_cvt_pk_u8_f32(d, 3, v);
+}
+
+// One horizontal item: K output pixels of output row y from column x (item j of the
+// strip), read from the LDS row `row` of packed intermediate bytes.
+template <int B, int WIDE, int TIGHT, bool MEM, bool NTS>
+__device__ __forceinline__ void reduce2_hitem(const Reduce2Args &a, int img, const uint32_t *row, int j, int x,
+                                              int y, float c0, float c1, float c3, float c5, float bias) {
+    using G = R2<B, WIDE, TIGHT>;
+    constexpr int K = G::K;
+    constexpr int W0 = (B * 2 * K) / 4;  // window start (dwords) per item
+    uint32_t win[13];
+    if (B == 3) {
+        const uint2 *r2 = reinterpret_cast<const uint2 *>(row + W0 * j);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const uint2 dd = r2[q];
+            win[2 * q] = dd.x;
+            win[2 * q + 1] = dd.y;
+        }
+        win[12] = row[W0 * j + 12];
+    } else {
+        const uint4 *r4 = reinterpret_cast<const uint4 *>(row + W0 * j);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint4 dd = r4[q];
+            win[4 * q] = dd.x, win[4 * q + 1] = dd.y, win[4 * q + 2] = dd.z, win[4 * q + 3] = dd.w;
+        }
+        win[12] = row[W0 * j + 12];
+    }
+    float o[K][B];
+    if (MEM) {  // diagnostic: skip the arithmetic, keep the LDS reads and stores
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int c = 0; c < B; ++c) o[k][c] = __uint_as_float(win[(k * B + c) % 13] & 0x437f0000u);
+    } else
+#pragma unroll
+    for (int c = 0; c < B; ++c) {
+        // px[t]: intermediate pixel 2x - 5 + t of channel c
+        float px[2 * K + 9];
+#pragma unroll
+        for (int t = 0; t < 2 * K + 9; ++t) {
+            const int lb = B * t + c + G::OFF0;
+            const uint32_t dd = win[lb >> 2];
+            switch (lb & 3) {
+                case 0: px[t] = ubyte_once<0>(dd); break;
+                case 1: px[t] = ubyte_once<1>(dd); break;
+                case 2: px[t] = ubyte_once<2>(dd); break;
+                default: px[t] = ubyte_once<3>(dd); break;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int m = 2 * k + 5;
+            o[k][c] = tap7(c0, c1, c3, c5, bias, px[m], px[m - 1], px[m + 1], px[m - 3], px[m + 3], px[m - 5],
+                           px[m + 5]);
+        }
+    }
+    u8 *q = a.out + img * a.out_img + (static_cast<size_t>(y) * a.ow + x) * B;
+    const bool full = x + K <= a.ow;
+    if (B == 3) {
+        const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[1][0]);
+        const uint32_t d1 = pack4b(o[1][1], o[1][2], o[2][0], o[2][1]);
+        const uint32_t d2 = pack4b(o[2][2], o[3][0], o[3][1], o[3][2]);
+        if (full && (reinterpret_cast<uintptr_t>(q) & 3u) == 0) {
+            if (NTS) {
+                typedef uint32_t u3v __attribute__((ext_vector_type(3)));
+                __builtin_nontemporal_store(u3v{d0, d1, d2}, reinterpret_cast<u3v *>(q));
+            } else {
+                *reinterpret_cast<uint3 *>(q) = uint3{d0, d1, d2};
+            }
+        } else {
+            const uint32_t dd[3] = {d0, d1, d2};
+            const int nb = (full ? K : a.ow - x) * B;
+            for (int i = 0; i < nb; ++i) q[i] = static_cast<u8>(dd[i >> 2] >> (8 * (i & 3)));
+        }
+    } else {
+        const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[0][3]);
+        const uint32_t d1 = pack4b(o[1][0], o[1][1], o[1][2], o[1][3]);
+        uint32_t *q32 = reinterpret_cast<uint32_t *>(q);
+        if (full && (reinterpret_cast<uintptr_t>(q) & 7u) == 0) {
+            *reinterpret_cast<uint2 *>(q) = uint2{d0, d1};
+        } else {
+            q32[0] = d0;
+            if (full) q32[1] = d1;
+        }
+    }
 }
 
 template <int B, int R, bool PF, bool PK, bool MEM, int LAUX, bool NTS, int WIDE, int TIGHT>
@@ -247,88 +341,121 @@ __device__ __forceinline__ void reduce2_tile(const Reduce2Args &a, int img, int 
             const int x = x0 + K * j;
             const int y = yc + u;
             if (y >= a.y_end || x >= a.x_end) continue;
-            const uint32_t *row = L + u * kPitch;
-            constexpr int W0 = (B * 2 * K) / 4;  // window start (dwords) per item
-            uint32_t win[13];
-            if (B == 3) {
-                const uint2 *r2 = reinterpret_cast<const uint2 *>(row + W0 * j);
-#pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    const uint2 dd = r2[q];
-                    win[2 * q] = dd.x;
-                    win[2 * q + 1] = dd.y;
-                }
-                win[12] = row[W0 * j + 12];
-            } else {
-                const uint4 *r4 = reinterpret_cast<const uint4 *>(row + W0 * j);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const uint4 dd = r4[q];
-                    win[4 * q] = dd.x, win[4 * q + 1] = dd.y, win[4 * q + 2] = dd.z, win[4 * q + 3] = dd.w;
-                }
-                win[12] = row[W0 * j + 12];
-            }
-            float o[K][B];
-            if (MEM) {  // diagnostic: skip the arithmetic, keep the LDS reads and stores
-#pragma unroll
-                for (int k = 0; k < K; ++k)
-#pragma unroll
-                    for (int c = 0; c < B; ++c) o[k][c] = __uint_as_float(win[(k * B + c) % 13] & 0x437f0000u);
-            } else
-#pragma unroll
-            for (int c = 0; c < B; ++c) {
-                // px[t]: intermediate pixel 2x - 5 + t of channel c
-                float px[2 * K + 9];
-#pragma unroll
-                for (int t = 0; t < 2 * K + 9; ++t) {
-                    const int lb = B * t + c + G::OFF0;
-                    const uint32_t dd = win[lb >> 2];
-                    switch (lb & 3) {
-                        case 0: px[t] = ubyte_once<0>(dd); break;
-                        case 1: px[t] = ubyte_once<1>(dd); break;
-                        case 2: px[t] = ubyte_once<2>(dd); break;
-                        default: px[t] = ubyte_once<3>(dd); break;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const int m = 2 * k + 5;
-                    o[k][c] = tap7(c0, c1, c3, c5, bias, px[m], px[m - 1], px[m + 1], px[m - 3], px[m + 3],
-                                   px[m - 5], px[m + 5]);
-                }
-            }
-            u8 *q = a.out + img * a.out_img + (static_cast<size_t>(y) * a.ow + x) * B;
-            const bool full = x + K <= a.ow;
-            if (B == 3) {
-                const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[1][0]);
-                const uint32_t d1 = pack4b(o[1][1], o[1][2], o[2][0], o[2][1]);
-                const uint32_t d2 = pack4b(o[2][2], o[3][0], o[3][1], o[3][2]);
-                if (full && (reinterpret_cast<uintptr_t>(q) & 3u) == 0) {
-                    if (NTS) {
-                        typedef uint32_t u3v __attribute__((ext_vector_type(3)));
-                        __builtin_nontemporal_store(u3v{d0, d1, d2}, reinterpret_cast<u3v *>(q));
-                    } else {
-                        *reinterpret_cast<uint3 *>(q) = uint3{d0, d1, d2};
-                    }
-                } else {
-                    const uint32_t dd[3] = {d0, d1, d2};
-                    const int nb = (full ? K : a.ow - x) * B;
-                    for (int i = 0; i < nb; ++i) q[i] = static_cast<u8>(dd[i >> 2] >> (8 * (i & 3)));
-                }
-            } else {
-                const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[0][3]);
-                const uint32_t d1 = pack4b(o[1][0], o[1][1], o[1][2], o[1][3]);
-                uint32_t *q32 = reinterpret_cast<uint32_t *>(q);
-                if (full && (reinterpret_cast<uintptr_t>(q) & 7u) == 0) {
-                    *reinterpret_cast<uint2 *>(q) = uint2{d0, d1};
-                } else {
-                    q32[0] = d0;
-                    if (full) q32[1] = d1;
-                }
-            }
+            reduce2_hitem<B, WIDE, TIGHT, MEM, NTS>(a, img, L + u * kPitch, j, x, y, c0, c1, c3, c5, bias);
         }
         // double-buffered LDS: the next vertical pass writes the other buffer, whose
         // readers all finished before this chunk's barrier
+    }
+}
+
+// Vertical pass of the one-pass tile over NR (12 or 24) output rows from y0: one burst
+// of raw loads (the five ring rows and the first 12 odd / even pairs, nothing converted
+// before all are issued), then NR rows of straight-line code.  A consumed register pair
+// is refilled with the row 12 ahead while rows remain, so the 24-row pass keeps 24
+// loads in flight and every wait is a counted one.
+template <int NR, int ND, int kThreads, int kPitch, class LoadRow>
+__device__ __forceinline__ void reduce2_vpass(const LoadRow &load_row, int y0, int tid, float c0, float c1,
+                                              float c3, float c5, float bias, uint32_t *L) {
+    constexpr int R = kR;
+    static_assert(NR == R || NR == 2 * R, "one or two chunks");
+    uint32_t r5[5], odd[R], even[R];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) r5[k] = load_row(2 * (y0 - 3 + k) + 1);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        odd[u] = load_row(2 * (y0 + u + 2) + 1);
+        even[u] = load_row(2 * (y0 + u));
+    }
+    // odd-row ring: slot s holds odd row 2m+1 with m = s (mod 6); y0 % 6 == 0
+    f4v ring[6];
+    ring[3] = cvt4_once(r5[0]);
+    ring[4] = cvt4_once(r5[1]);
+    ring[5] = cvt4_once(r5[2]);
+    ring[0] = cvt4_once(r5[3]);
+    ring[1] = cvt4_once(r5[4]);
+    ring[2] = f4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < NR; ++u) {
+        const int s = u % R;
+        ring[(u + 2) % 6] = cvt4_once(odd[s]);
+        const f4v e = cvt4_once(even[s]);
+        if (u + R < NR) {  // rotate: this register pair now fetches the row 12 ahead
+            odd[s] = load_row(2 * (y0 + R + u + 2) + 1);
+            even[s] = load_row(2 * (y0 + R + u));
+        }
+        const f4v m5 = ring[(u + 3) % 6], m3 = ring[(u + 4) % 6], m1 = ring[(u + 5) % 6];
+        const f4v p1 = ring[u % 6], p3 = ring[(u + 1) % 6], p5 = ring[(u + 2) % 6];
+        const uint32_t d = pack4b(tap7(c0, c1, c3, c5, bias, e.x, m1.x, p1.x, m3.x, p3.x, m5.x, p5.x),
+                                  tap7(c0, c1, c3, c5, bias, e.y, m1.y, p1.y, m3.y, p3.y, m5.y, p5.y),
+                                  tap7(c0, c1, c3, c5, bias, e.z, m1.z, p1.z, m3.z, p3.z, m5.z, p5.z),
+                                  tap7(c0, c1, c3, c5, bias, e.w, m1.w, p1.w, m3.w, p3.w, m5.w, p5.w));
+        if (ND >= kThreads || tid < ND) L[u * kPitch + tid] = d;
+    }
+}
+
+// The one-pass tile (the shipped body): the geometry, arithmetic and LDS bytes of
+// reduce2_tile at R = 12 with register prefetch, but the tile's 24 rows go through one
+// load burst, one vertical pass, one barrier and one horizontal pass.  The 2 * R * kPitch
+// dwords are one 24-row image; the kernel ends after its output stores, so no wait covers
+// a store.  A band of at most 12 rows (the last tile of a window, a short image) takes
+// the 12-row vertical pass.
+template <int B, int WIDE, int TIGHT>
+__device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, int strip, int band,
+                                                uint32_t *lds) {
+    using G = R2<B, WIDE, TIGHT>;
+    constexpr int kThreads = G::kThreads, kPitch = G::kPitch;
+    constexpr int TW = G::TW, K = G::K;
+    const int tid = threadIdx.x;
+    const int x0 = (a.s_base + strip) * TW;
+    const int row_bytes = a.w * B;
+    const int px0 = 2 * x0 - 5;          // first intermediate pixel of the strip
+    const int base = (B * px0) & ~3;     // floor to a dword (two's complement)
+    const int byte0 = base + 4 * tid;
+    const bool vlane = tid < G::ND && byte0 >= 0 && byte0 + 4 <= row_bytes;
+    // raw buffer loads as in reduce2_tile: lanes outside the row read 0
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<u8 *>(a.in + img * a.in_img), 0, static_cast<int>(a.in_img), 0x00020000);
+    const uint32_t voff = vlane ? static_cast<uint32_t>(byte0) : 0x80000000u;
+    const int y0 = a.y_base + band * a.band_rows;
+    const int y1 = min(y0 + a.band_rows, a.y_end);
+    const int rows = y1 - y0;            // 1 .. 24
+    const float c0 = a.c0, c1 = a.c1, c3 = a.c3, c5 = a.c5, bias = a.bias;
+    const int nl = px0 < 0 ? -px0 : 0;
+    const int x_last = min(x0 + TW, a.x_end) - 1;
+    const int fr = a.w - px0;                                   // LDS index of pixel w
+    const int fr_end = min(2 * x_last + 5 - px0, G::NPX - 1);   // last LDS pixel read
+    const int nr = fr_end >= fr ? fr_end - fr + 1 : 0;
+
+    auto load_row = [&](int r) -> uint32_t {
+        r = clampi(r, 0, a.h - 1);
+        return static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, r * row_bytes, 0));
+    };
+    // ---- vertical pass: all intermediate rows of the tile -> LDS (packed uchar) ----
+    if (rows > kR) reduce2_vpass<2 * kR, G::ND, kThreads, kPitch>(load_row, y0, tid, c0, c1, c3, c5, bias, lds);
+    else reduce2_vpass<kR, G::ND, kThreads, kPitch>(load_row, y0, tid, c0, c1, c3, c5, bias, lds);
+    if (nl > 0 || nr > 0) {  // replicate the edge pixels (EXTEND_COPY) inside the LDS image
+        __syncthreads();
+        u8 *Lb = reinterpret_cast<u8 *>(lds);
+        const int nfill = nl + nr;
+        for (int i = tid; i < rows * nfill * B; i += kThreads) {
+            const int u = i / (nfill * B);
+            const int rem = i - u * nfill * B;
+            const int f = rem / B, c = rem - f * B;
+            const int dst = f < nl ? f : fr + (f - nl);
+            const int srcp = f < nl ? nl : fr - 1;
+            Lb[u * kPitch * 4 + B * dst + G::OFF0 + c] = Lb[u * kPitch * 4 + B * srcp + G::OFF0 + c];
+        }
+    }
+    __syncthreads();
+    // ---- horizontal pass: K output pixels per item, one channel at a time ----
+    constexpr int items_per_row = TW / K;
+    for (int it = tid; it < rows * items_per_row; it += kThreads) {
+        const int u = it / items_per_row;
+        const int j = it - u * items_per_row;
+        const int x = x0 + K * j;
+        const int y = y0 + u;
+        if (x >= a.x_end) continue;
+        reduce2_hitem<B, WIDE, TIGHT, false, false>(a, img, lds + u * kPitch, j, x, y, c0, c1, c3, c5, bias);
     }
 }
 
@@ -344,6 +471,8 @@ __device__ __forceinline__ void reduce2_tile(const Reduce2Args &a, int img, int 
 // strips four times as wide.  Measured in
 // profiles/r01/v7_variants_ab.log: the memory-only build is no faster than the
 // full one (the arithmetic is hidden), packed math and nt hints lose.
+// bit 9: the chunk-loop body reduce2_tile (the bits above select its build); without it
+// the one-pass body reduce2_onepass at this strip width, which is R = 12 with prefetch.
 template <int B, int VAR>
 __global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kThreads) k_reduce2x2(Reduce2Args a) {
     constexpr int WIDE = (VAR & 128) ? 2 : (VAR & 64) ? 1 : 0;
@@ -369,7 +498,12 @@ __global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kTh
         band = rest % a.n_bands;
         img = rest / a.n_bands;
     }
-    reduce2_tile<B, R, PF, PK, MEM, LAUX, NTS, WIDE, TIGHT>(a, img, strip, band, lds);
+    if constexpr ((VAR & 512) != 0) {
+        reduce2_tile<B, R, PF, PK, MEM, LAUX, NTS, WIDE, TIGHT>(a, img, strip, band, lds);
+    } else {
+        static_assert(R == kR && PF && !PK && !MEM && LAUX == 0 && !NTS, "the one-pass body has one build");
+        reduce2_onepass<B, WIDE, TIGHT>(a, img, strip, band, lds);
+    }
 }
 
 
@@ -526,19 +660,25 @@ bool reduce2_eligible(const u8 *in, int w, int h, int b, double hs, double vs) {
     return shape_ok;
 }
 
-// k_reduce2x2 build variant.  Only the shipped one (66) is compiled now; the r01 / r02
+// k_reduce2x2 build variant: 66, the one-pass body (shipped), and 66 | 512 = 578, the
+// chunk-loop body it replaced (the A/B arm of scripts/ab_r2_onepass.py, and the body that
+// honours MIPX_R2_BAND: setting that knob selects it).  The r01 / r02
 // A/B builds (strip widths, register prefetch, LDS row strides) are recorded under
 // profiles/r01 and profiles/r02 (scripts/ab_reduce.py, in git history, ran them).  r06's
 // cache-policy A/B compiled 66 | 16 / 32 / 48 (82 / 98 / 114: non-temporal loads / stores /
 // both, the LAUX / NTS parameters of reduce2_tile) as extra cases here: -15 % / +0.2 % /
 // -14 % (profiles/r06/c2_nt_ab.jsonl), so none is kept.
 constexpr int kR2Default = 66;  // wide strips, R = 12 + register prefetch: measured best (profiles/r01/v10_wide_ab.log)
+constexpr int kR2Loop = kR2Default | 512;
 int reduce2_variant() {
+    const char *eb = tune_env("MIPX_R2_BAND");
+    if (eb && *eb) return kR2Loop;  // only the chunk loop walks bands of other heights
     const char *e = tune_env("MIPX_R2_VARIANT");
     if (!e || !*e) return kR2Default;
     const int v = std::atoi(e);
     switch (v) {
-        case 66: return v;
+        case kR2Default:
+        case kR2Loop: return v;
         default: return kR2Default;
     }
 }
@@ -608,6 +748,7 @@ int reduce2_window_launch(const u8 *in, u8 *out, int n, int w, int h, int b, int
     }
     switch (var) {
         MIPX_R2(66)
+        MIPX_R2(578)
         default: return MIPX_EINVAL;
     }
 #undef MIPX_R2
