@@ -405,11 +405,12 @@ def _huff_lookup(counts, symbols):
     return lut.tolist()
 
 
-def _jpeg_segments(buf: bytes, dht=None):
+def _jpeg_segments(buf: bytes, dht=None, span=None):
     """What decode_jpeg_coefs needs of a file's headers, or None for a file it does not take:
     (w, h, components [(id, h, v, tq, td, ta)], tables {tq: 64 natural-order values}, Huffman
     lookups {Tc/Th byte: lookup}, restart interval, the entropy-coded intervals).  dht: a dict
-    that takes the Huffman tables as the file has them, {Tc/Th byte: (16 counts, symbols)}."""
+    that takes the Huffman tables as the file has them, {Tc/Th byte: (16 counts, symbols)}.
+    span: a list that takes the offsets in buf of the scan's first byte and of its closing FF D9."""
     import re
     if buf[:2] != b"\xff\xd8":
         return None
@@ -495,6 +496,8 @@ def _jpeg_segments(buf: bytes, dht=None):
             break
     if end != 0xD9:                                          # truncated, or another scan follows
         return None
+    if span is not None:
+        span[:] = [p, at - 2]
     return w, h, full, qt, huff, restart, parts
 
 
@@ -605,7 +608,7 @@ JPEGH_HEADER_BYTES = 1504   # MIPX_JPEGH_HEADER_BYTES
 JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
 
 
-def jpeg_huff_slot(buf: bytes):
+def jpeg_huff_slot(buf: bytes, restart: bool = False):
     """A JPEG's entropy-coded scan as the file has it, packed for the engine's entropy decoder
     (MIPX_JPEGH_HEADER_BYTES in include/mipx.h): (slot, layout) with slot a 1-D uint8 array of
     the scan's length, the quantisation tables of Y, Cb, Cr, the components' Huffman table
@@ -613,26 +616,35 @@ def jpeg_huff_slot(buf: bytes):
     (1504 + the coefficients' size; slot[:1504 + length] is all the engine reads).  The host
     reads markers only.  None (it never raises) for every file decode_jpeg_coefs does not take
     by its headers, and for files with a restart interval, a Huffman table index above 1 or a
-    scan longer than the coefficients."""
+    scan longer than the coefficients.
+
+    restart=True takes files with a restart interval (DRI) too: the interval, in MCUs, goes into
+    the header at offset 4 (0 for a file without one) and the scan is the file's bytes between the
+    SOS segment and FF D9 as they are, restart markers included; the engine checks the markers."""
     try:
-        dht = {}
-        seg = _jpeg_segments(bytes(buf), dht)
+        buf = bytes(buf)
+        dht, span = {}, []
+        seg = _jpeg_segments(buf, dht, span)
         if seg is None:
             return None
-        w, h, comps, qt, _, restart, parts = seg
+        w, h, comps, qt, _, interval, parts = seg
         samp = tuple((c[1], c[2]) for c in comps)
         layout = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}.get(samp)
-        if layout is None or restart != 0 or len(parts) != 1:
+        if layout is None:
+            return None
+        if not restart and (interval != 0 or len(parts) != 1):
             return None
         if any(c[4] > 1 or (c[5] & 15) > 1 for c in comps):
             return None
         geo, _, _ = _jpegc_geometry(w, h, layout)
         cap = 128 * sum(wb * hb for wb, hb, _ in geo)
-        scan = parts[0]
+        scan = buf[span[0]:span[1]] if restart else parts[0]
         if len(scan) > cap:
             return None
         slot = np.zeros(JPEGH_HEADER_BYTES + cap, np.uint8)
         slot[0:4] = np.frombuffer(len(scan).to_bytes(4, "little"), np.uint8)
+        if restart:
+            slot[4:8] = np.frombuffer(interval.to_bytes(4, "little"), np.uint8)
         slot[16:400] = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel().view(np.uint8)
         slot[400:406] = [c[4] for c in comps] + [c[5] & 15 for c in comps]
         for i, key in enumerate((0x00, 0x01, 0x10, 0x11)):

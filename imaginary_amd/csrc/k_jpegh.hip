@@ -12,6 +12,12 @@
 //   k_jpegh_ffcount    FF 00 pairs per kChunk bytes of the stuffed scan; FF + anything else: BAD
 //   k_jpegh_prep       one workgroup per image: the scan of those counts, the unstuffed length,
 //                      the Huffman tables' validity
+//   k_jpegr_index, k_jpegr_decode
+//                      the images with restart intervals, whose codeword boundaries are their
+//                      markers: see "restart intervals" below.  For them the two kernels above
+//                      count and check the markers instead, every kernel below returns at once
+//                      (k_jpegh_dcwrite after their quantisation tables and final status), and
+//                      these two return at once for every other image
 //   k_jpegh_unstuff    the scan without the stuffed zeros into the workspace
 //   k_jpegh_sync x (1 + kJpeghRounds)
 //                      lane i decodes subsequence i from its entry state (values skipped, blocks
@@ -54,6 +60,10 @@ constexpr uint32_t kSubBits = 8u * kJpeghSub;
 constexpr uint32_t kChunk = 4u * kLanes;     // stuffed bytes per workgroup: 4 per lane
 constexpr uint32_t kLut = 9;                 // bits of the first-level Huffman look-up
 constexpr uint32_t kNone = 0xffffffffu;
+// The status of a restart image between k_jpegh_prep and k_jpegh_dcwrite, never seen by a caller: the
+// kernels of the synchronising path skip it as they skip every status but OK
+constexpr uint32_t kPending = 3u;
+static_assert(kPending != MIPX_JPEGH_OK && kPending != MIPX_JPEGH_UNSYNCED && kPending != MIPX_JPEGH_BAD, "internal");
 // dwords of LDS per lane of a decoding kernel: the subsequence's 32, the 2 a look-ahead reads past
 // them, and one more so that the lanes of a wave, each at its own bit, read 64 different banks
 constexpr uint32_t kStagePitch = kJpeghSub / 4u + 3u;
@@ -63,8 +73,9 @@ static_assert(kLanes == 256, "block_scan sums four waves");
 
 struct JpeghInfo {  // per image, zeroed every call
     uint32_t ulen;   // bytes of the unstuffed stream
-    uint32_t flags;  // 1: the slot cannot be decoded (set by any workgroup of the image)
-    uint32_t pad[6];
+    uint32_t flags;  // 1: the slot cannot be decoded (k_jpegh_ffcount); 2: the same, found on the restart path
+    uint32_t rst;    // the restart interval in MCUs of an image on the restart path (k_jpegh_prep), else 0
+    uint32_t pad[5];
 };
 static_assert(sizeof(JpeghInfo) == 32, "JpeghWork sizes the records");
 
@@ -87,6 +98,7 @@ struct JpeghArgs {
     uint32_t n, cap, sstride;
     uint32_t chunks, seqs, tiles;  // per image, by the capacity (W's, the strides of the arrays above)
     uint32_t blocks;               // of this image's scan, dummy ones included
+    uint32_t mcus;                 // of this image's scan
     uint32_t wblocks;              // the stride of dcdiff
     uint32_t ywb, yhb, mw;
     uint32_t cb_off, cr_off;       // byte offsets of Cb and Cr in the payload's coefficients
@@ -150,6 +162,32 @@ __device__ __forceinline__ uint32_t slot_length(const JpeghArgs &a, const u8 *sl
     return length > a.cap ? 0u : length;  // k_jpegh_prep reports it; nothing reads past the slot
 }
 
+// The slot's restart interval in MCUs when the image takes the restart path: 1..65535 and two
+// intervals or more (K = ceil(mcus / Ri) >= 2).  Else 0: the image is an ordinary scan.
+__device__ __forceinline__ uint32_t slot_restart(const JpeghArgs &a, const u8 *slot) {
+    const uint32_t ri = load_u32(slot + 4u);
+    return ri >= 1u && ri <= 65535u && ri < a.mcus ? ri : 0u;
+}
+
+// The restart path's view of the lane's 4 stuffed bytes from `first` on: bit j set where an FF that
+// D0..D7 follows starts (an FF is always the first byte of a pair: no pair ends in one), and whether
+// one of them is an FF that neither 00 nor D0..D7 follows inside `length`.  Reads no byte at or past
+// length.
+__device__ __forceinline__ uint32_t marks4(const u8 *scan, uint32_t first, uint32_t length, bool *other) {
+    uint32_t marks = 0;
+    *other = false;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t i = first + j;
+        if (i < length && scan[i] == 0xffu) {
+            const uint32_t next = i + 1u < length ? scan[i + 1u] : 0xffu;
+            if ((next & 0xf8u) == 0xd0u) marks |= 1u << j;
+            else if (next != 0u) *other = true;
+        }
+    }
+    return marks;
+}
+
 __global__ void __launch_bounds__(kLanes) k_jpegh_ffcount(const JpeghArgs a) {
     __shared__ uint32_t wsum[kLanes / 64];
     const uint32_t img = blockIdx.y, chunk = blockIdx.x;
@@ -158,7 +196,10 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_ffcount(const JpeghArgs a) {
     if (static_cast<u64>(chunk) * kChunk >= length) return;
     uint32_t bytes[4];
     bool marker;
-    const uint32_t drop = stuffed4(slot + kJpeghHeader, chunk * kChunk + threadIdx.x * 4u, length, bytes, &marker);
+    // an ordinary scan: the stuffed zeros; a restart image: the restart markers
+    const uint32_t first = chunk * kChunk + threadIdx.x * 4u;
+    const uint32_t drop = slot_restart(a, slot) ? marks4(slot + kJpeghHeader, first, length, &marker)
+                                                : stuffed4(slot + kJpeghHeader, first, length, bytes, &marker);
     uint32_t total;
     block_scan<uint32_t>(__builtin_popcount(drop), wsum, &total);
     if (threadIdx.x == 0) a.chunk_sums[static_cast<size_t>(img) * a.chunks + chunk] = total;
@@ -216,7 +257,12 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_prep(const JpeghArgs a) {
     const bool any_bad = __syncthreads_or(bad);
     if (tid != 0) return;
     a.info[img].ulen = length - carry;
-    if (any_bad || a.info[img].flags) a.status[img] = MIPX_JPEGH_BAD;
+    // a restart image: `carry` is its markers, one less than its intervals
+    const uint32_t ri = load_u32(slot + 4u), rst = slot_restart(a, slot);
+    a.info[img].rst = rst;
+    const bool count_bad = rst != 0u && carry != (a.mcus + rst - 1u) / rst - 1u;
+    if (any_bad || a.info[img].flags || ri > 65535u || count_bad) a.status[img] = MIPX_JPEGH_BAD;
+    else if (rst != 0u) a.status[img] = kPending;  // k_jpegr_index, k_jpegr_decode take it; k_jpegh_dcwrite ends it
 }
 
 __global__ void __launch_bounds__(kLanes) k_jpegh_unstuff(const JpeghArgs a) {
@@ -334,13 +380,13 @@ struct Step {
     int coef;
 };
 
-// One code and its value bits.  Total: every input moves pos by 1..31 bits and leaves a state.
+// One code and its value bits, of v, the stream's next 32 bits.  Total: every input moves pos by
+// 1..31 bits and leaves a state.
 template <int LAYOUT>
-__device__ __forceinline__ Step step(State &s, const Huff &H, const uint32_t *words, uint32_t origin, uint32_t total) {
+__device__ __forceinline__ Step step_bits(State &s, const Huff &H, const uint32_t v) {
     constexpr uint32_t kPerMcu = LAYOUT == MIPX_YCC_444 ? 3u : 6u;
     Step r;
     r.error = false, r.value = false, r.block_end = false, r.k = 0, r.coef = 0;
-    const uint32_t v = peek32(words, s.pos - origin, total - s.pos);
     const uint32_t t = s.k == 0u ? (H.dcsel >> s.b & 1u) : 2u + (H.acsel >> s.b & 1u);
     uint32_t e = H.first[t][v >> (32u - kLut)];
     if (e == 0u) {
@@ -393,6 +439,11 @@ __device__ __forceinline__ Step step(State &s, const Huff &H, const uint32_t *wo
         r.block_end = true;
     }
     return r;
+}
+
+template <int LAYOUT>
+__device__ __forceinline__ Step step(State &s, const Huff &H, const uint32_t *words, uint32_t origin, uint32_t total) {
+    return step_bits<LAYOUT>(s, H, peek32(words, s.pos - origin, total - s.pos));
 }
 
 struct Span {  // an image's stream, as every decoding workgroup sees it
@@ -626,6 +677,11 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_dcwrite(const JpeghArgs a) {
         const u8 *q = a.slots + static_cast<size_t>(img) * (kJpeghHeader + static_cast<size_t>(a.cap)) + kQuantOff;
         payload[2u * tid] = q[2u * tid], payload[2u * tid + 1u] = q[2u * tid + 1u];
     }
+    if (a.info[img].rst) {  // a restart image: k_jpegr_decode wrote its DCs; this last launch ends kPending
+        if (tile == 0u && tid == 0u && a.status[img] == kPending)
+            a.status[img] = a.info[img].flags & 2u ? MIPX_JPEGH_BAD : MIPX_JPEGH_OK;
+        return;
+    }
     if (a.status[img] != MIPX_JPEGH_OK) return;
     const bool valid = cur < a.blocks;
     const int d = valid ? a.dcdiff[static_cast<size_t>(img) * a.wblocks + cur] : 0;
@@ -645,6 +701,137 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_dcwrite(const JpeghArgs a) {
     }
     const int16_t v = static_cast<int16_t>(dc);
     __builtin_memcpy(payload + MIPX_JPEGD_HEADER_BYTES + dst, &v, 2);
+}
+
+// ---- restart intervals ----------------------------------------------------------------------
+// An image whose slot names a restart interval (JpeghInfo::rst != 0) has its codeword boundaries in
+// the byte stream: interval k starts behind marker k - 1, at block 0 of MCU k * rst, with the three
+// DC predictors 0.  k_jpegh_prep leaves it the status kPending, which keeps it out of the kernels
+// of the synchronising path; these two kernels report what they find in JpeghInfo::flags, and
+// k_jpegh_dcwrite, the last launch, turns that into OK or BAD.  Its interval table (the first byte
+// of every interval) lies in the image's part of `counts`, which only the synchronising path
+// uses: K <= mcus <= 3 ywb yhb <= seqs * kLanes.
+
+// Every marker's place into the table, and its number checked: marker k is FF D0 + (k & 7).
+__global__ void __launch_bounds__(kLanes) k_jpegr_index(const JpeghArgs a) {
+    __shared__ uint32_t wsum[kLanes / 64];
+    const uint32_t img = blockIdx.y;
+    if (a.status[img] != kPending) return;  // nothing changes it during this launch
+    const uint32_t rst = a.info[img].rst;
+    const u8 *slot = a.slots + static_cast<size_t>(img) * (kJpeghHeader + static_cast<size_t>(a.cap));
+    const uint32_t length = slot_length(a, slot);
+    const u8 *scan = slot + kJpeghHeader;
+    uint32_t *table = a.counts + static_cast<size_t>(img) * a.seqs * kLanes;
+    const uint32_t intervals = (a.mcus + rst - 1u) / rst;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) table[0] = 0u;
+    bool bad = false;
+    // the grid is a fixed number of workgroups per image, not one per chunk of the capacity: an
+    // ordinary image pays a handful of workgroups that return at once
+    const uint32_t count = (length + kChunk - 1u) / kChunk;  // <= a.chunks: length <= cap
+    for (uint32_t chunk = blockIdx.x; chunk < count; chunk += gridDim.x) {
+        const uint32_t first = chunk * kChunk + threadIdx.x * 4u;
+        bool other;
+        const uint32_t marks = marks4(scan, first, length, &other);
+        uint32_t total;
+        uint32_t k = a.chunk_offs[static_cast<size_t>(img) * a.chunks + chunk] +
+                     block_scan<uint32_t>(__builtin_popcount(marks), wsum, &total);
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            if (!(marks >> j & 1u)) continue;
+            // k_jpegh_prep counted intervals - 1 markers, so k + 1 < intervals; first + j + 1 < length
+            if (k + 1u < intervals) table[k + 1u] = first + j + 2u;
+            if (scan[first + j + 1u] != 0xd0u + (k & 7u)) bad = true;
+            ++k;
+        }
+    }
+    if (bad) atomicOr(&a.info[img].flags, 2u);
+}
+
+// One lane per interval.  The lane reads its interval's stuffed bytes from the slot, dropping the 00
+// behind an FF as it refills its bit buffer, walks exactly its MCUs by the rules of step_bits, keeps
+// the three DCs and stores every real block's DC and non-zero ACs into the payload (its quantisation
+// tables are k_jpegh_dcwrite's, as for every image).  Any broken rule, a DC outside int16 and an
+// interval that ends before its last block are BAD; bits behind the last block are ignored.  A step
+// takes a bit or more, so the loop ends within the interval's bits.
+template <int LAYOUT>
+__global__ void __launch_bounds__(kLanes) k_jpegr_decode(const JpeghArgs a) {
+    constexpr uint32_t kPerMcu = LAYOUT == MIPX_YCC_444 ? 3u : 6u;
+    __shared__ Huff H;
+    const uint32_t img = blockIdx.y, tid = threadIdx.x;
+    if (a.status[img] != kPending) return;  // nothing changes it during this launch
+    const uint32_t rst = a.info[img].rst;
+    const u8 *slot = a.slots + static_cast<size_t>(img) * (kJpeghHeader + static_cast<size_t>(a.cap));
+    u8 *payload = a.payloads + static_cast<size_t>(img) * (MIPX_JPEGD_HEADER_BYTES + static_cast<size_t>(a.cap));
+    const uint32_t intervals = (a.mcus + rst - 1u) / rst;
+    if (blockIdx.x * kLanes >= intervals) return;
+    load_tables<LAYOUT>(slot, H);
+    const uint32_t k = blockIdx.x * kLanes + tid;
+    if (k >= intervals) return;
+    const uint32_t length = slot_length(a, slot);
+    const uint32_t *table = a.counts + static_cast<size_t>(img) * a.seqs * kLanes;
+    const uint32_t start = table[k];
+    const uint32_t end = k + 1u < intervals ? table[k + 1u] - 2u : length;  // the marker's FF, or the scan's end
+    if (start > end || end > length) {  // not with the table k_jpegr_index makes of K - 1 markers
+        atomicOr(&a.info[img].flags, 2u);
+        return;
+    }
+    const u8 *scan = slot + kJpeghHeader;
+    u8 *coefs = payload + MIPX_JPEGD_HEADER_BYTES;
+    uint32_t cur = k * rst * kPerMcu;  // the block the lane is in; k * rst < mcus
+    const uint32_t stop = cur + min(rst, a.mcus - k * rst) * kPerMcu;  // <= a.blocks
+    u64 buf = 0;         // the stream's next bits, the first in bit 63
+    uint32_t nbits = 0;  // bits of buf in use; behind the interval's last byte they are zeros
+    uint32_t real = 0;   // bits of the interval taken into buf so far
+    uint32_t pos = start;
+    int dc0 = 0, dc1 = 0, dc2 = 0;
+    State s;
+    s.pos = 0u, s.b = 0u, s.k = 0u;  // pos: bits consumed
+    uint32_t comp;
+    uint32_t dst = block_dst<LAYOUT>(a, cur, &comp);
+    bool bad = false;
+    const uint32_t bits = 8u * (end - start);  // cap < 2^29
+    for (uint32_t i = 0; i <= bits && cur < stop; ++i) {
+        while (nbits <= 56u) {
+            uint32_t b = 0;
+            if (pos < end) {
+                b = scan[pos++];
+                real += 8u;
+                if (b == 0xffu) ++pos;  // its stuffed 00: every other FF made the slot BAD before
+            }
+            buf |= static_cast<u64>(b) << (56u - nbits);
+            nbits += 8u;
+        }
+        const uint32_t before = s.pos;
+        const Step r = step_bits<LAYOUT>(s, H, static_cast<uint32_t>(buf >> 32));
+        const uint32_t used = s.pos - before;  // 1..31 <= nbits
+        buf <<= used, nbits -= used;
+        if (r.error || s.pos > real) {
+            bad = true;
+            break;
+        }
+        if (r.value) {
+            if (r.k == 0u) {
+                // a real block follows within the MCU, and its check keeps the sums inside an int
+                const int dc = comp == 0u ? (dc0 += r.coef) : comp == 1u ? (dc1 += r.coef) : (dc2 += r.coef);
+                if (dst != kNone) {
+                    if (dc < -32768 || dc > 32767) {
+                        bad = true;
+                        break;
+                    }
+                    const int16_t c = static_cast<int16_t>(dc);
+                    __builtin_memcpy(coefs + dst, &c, 2);
+                }
+            } else if (dst != kNone && r.coef != 0) {
+                const int16_t c = static_cast<int16_t>(r.coef);
+                __builtin_memcpy(coefs + dst + 2u * kNatural[r.k], &c, 2);  // dst + 128 <= cap
+            }
+        }
+        if (r.block_end) {
+            ++cur;
+            if (cur < stop) dst = block_dst<LAYOUT>(a, cur, &comp);
+        }
+    }
+    if (bad || cur < stop) atomicOr(&a.info[img].flags, 2u);
 }
 
 }  // namespace
@@ -680,22 +867,32 @@ int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, i
     a.cr_off = a.cb_off + cwb * chb * 128u;
     const unsigned long long blocks = static_cast<unsigned long long>(cwb) * chb * (sub ? 6u : 3u);
     a.blocks = static_cast<uint32_t>(blocks);
+    a.mcus = cwb * chb;
     // the grids of this image: by its own capacity, inside the workspace's strides
     const uint32_t chunks = (a.cap + kChunk - 1u) / kChunk;
     const uint32_t seqs = (a.cap + kJpeghSub * kLanes - 1u) / (kJpeghSub * kLanes);
     const uint32_t tiles = static_cast<uint32_t>((blocks + kLanes - 1u) / kLanes);
     if (a.cap > W.cap || a.cap >= (1u << 29) || blocks > W.blocks || chunks > W.chunks || seqs > W.seqs ||
-        tiles > W.tiles || !grid_ok(chunks) || !grid_ok(tiles))
+        tiles > W.tiles || !grid_ok(chunks) || !grid_ok(tiles) ||
+        a.mcus > W.seqs * kLanes)  // the interval table's room in `counts`
         return MIPX_EUNSUPPORTED;
     MIPX_HIP(hipMemsetAsync(d_status, 0, static_cast<size_t>(n) * 4, st));
     MIPX_HIP(hipMemsetAsync(work + W.info, 0, static_cast<size_t>(n) * sizeof(JpeghInfo), st));
     MIPX_HIP(hipMemsetAsync(d_payloads, 0, static_cast<size_t>(n) * (MIPX_JPEGD_HEADER_BYTES + static_cast<size_t>(a.cap)), st));
     const dim3 threads(kLanes), by_chunk(chunks, n), by_seq(seqs, n), by_tile(tiles, n), by_image(n);
+    const dim3 by_interval((a.mcus + kLanes - 1u) / kLanes, n);  // at most one interval per MCU; below tiles
+    const dim3 by_index(chunks < 128u ? chunks : 128u, n);       // k_jpegr_index strides over the chunks
     int e;
     hipLaunchKernelGGL(k_jpegh_ffcount, by_chunk, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_ffcount"))) return e;
     hipLaunchKernelGGL(k_jpegh_prep, by_image, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_prep"))) return e;
+    // the restart path: images with a restart interval finish here, every other leaves at once
+    hipLaunchKernelGGL(k_jpegr_index, by_index, threads, 0, st, a);
+    if ((e = launch_check("k_jpegr_index"))) return e;
+    if (sub) hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_420>, by_interval, threads, 0, st, a);
+    else hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_444>, by_interval, threads, 0, st, a);
+    if ((e = launch_check("k_jpegr_decode"))) return e;
     hipLaunchKernelGGL(k_jpegh_unstuff, by_chunk, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_unstuff"))) return e;
     for (uint32_t round = 0; round <= kJpeghRounds; ++round) {

@@ -613,7 +613,7 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
                   jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False,
-                  jpeg_huff: bool = False) -> Image:
+                  jpeg_huff: bool = False, jpeg_huff_restart: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -640,6 +640,9 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     jpeg_dct takes (with jpeg_dct_shrink, on the shrink-on-load ones too).  A file jpeg_huff_slot
     declines (restart intervals, more than two tables of a kind) and a scan the engine reports as not
     decodable (MIPX_EDATA) go on as jpeg_dct does; the bytes are the same either way.
+    jpeg_huff_restart: with jpeg_huff, files with a restart interval go to the engine as their scan too
+    (codec.jpeg_huff_slot(buf, restart=True)), one decoder per interval; a scan whose markers are not
+    the ones the interval asks for is MIPX_EDATA and goes on as jpeg_dct does.
     device_reencode: a 3-band JPEG that rotates and shrinks on load (_rotate_reencode_shrink_on_load)
     runs as one plan, the re-encode and the scaled decode as a MIPX_OP_JPEGRT step between the
     rotation and the rest: one upload, no host codec in between; the bytes are the same either way."""
@@ -680,8 +683,9 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
         px = None
         if take and jpeg_huff:
-            px = _with_scan(buf, lambda slot: process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq,
-                                                      jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan))
+            px = _with_scan(buf, jpeg_huff_restart,
+                            lambda slot: process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq,
+                                                 jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan))
         if px is None:
             dct = codec.decode_jpeg_coefs(buf) if take else None
             px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
@@ -690,9 +694,9 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         take = (jpeg_dct or jpeg_huff) and hdr.bands == 3 and itype == "jpeg"
         px = None
         if take and jpeg_huff:
-            px = _with_scan(buf, lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts,
-                                                      wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq,
-                                                      jpeg_scan=jpeg_scan))
+            px = _with_scan(buf, jpeg_huff_restart,
+                            lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts,
+                                                 wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq, jpeg_scan=jpeg_scan))
         dct = codec.decode_jpeg_coefs(buf) if take and px is None else None
         planes = codec.decode_ycc(buf) if px is None and dct is None and ycc and hdr.bands == 3 else None
         if px is not None:
@@ -715,10 +719,10 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     return _encode(px, t, quality, compression)
 
 
-def _with_scan(buf: bytes, run):
+def _with_scan(buf: bytes, restart: bool, run):
     """run((slot, layout)) of the file's entropy-coded scan; None where the file has no slot
     (codec.jpeg_huff_slot) or the engine could not decode it, and the caller goes on without."""
-    slot = codec.jpeg_huff_slot(buf)
+    slot = codec.jpeg_huff_slot(buf, restart=restart)
     if slot is None:
         return None
     try:

@@ -247,12 +247,19 @@ enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODA
 #define MIPX_JPEGD_HEADER_BYTES 384
 /* Entropy-coded JPEG input (mipx_op_jpegh_*): the file's scan bytes instead of its coefficients, a
  * fifth to a third of their size, so the host only reads markers.  The engine decodes a baseline
- * (or extended sequential) Huffman scan of three components, one interleaved scan without restart
- * markers, into exactly MIPX_OP_JPEGD's payload (PARITY_ASSUMPTIONS.md row 22).
+ * (or extended sequential) Huffman scan of three components, one interleaved scan with or without
+ * restart intervals, into exactly MIPX_OP_JPEGD's payload (PARITY_ASSUMPTIONS.md rows 22 and 23).
  *    One image's input is a slot of mipx_jpegh_bytes(w, h, layout) = MIPX_JPEGH_HEADER_BYTES +
  * mipx_jpegc_bytes(w, h, layout) bytes, all fields little-endian, starting on any byte:
  *      0  uint32 length: bytes of entropy-coded data behind the header, exactly as in the file
- *         between the SOS segment and FF D9 (stuffed); then three uint32 zeros
+ *         between the SOS segment and FF D9 (stuffed, restart markers included)
+ *      4  uint32 restart: the file's DRI value Ri in MCUs, 0 for a file without one; then two uint32
+ *         zeros.  With M the scan's MCUs (ceil(w/8) ceil(h/8) for 4:4:4, ceil(w/16) ceil(h/16) for
+ *         4:2:0) and K = ceil(M / Ri): Ri = 0, or Ri <= 65535 with K = 1, is an ordinary scan
+ *         without a marker.  Ri <= 65535 with K >= 2: the scan is K intervals with K - 1 two-byte
+ *         markers between them, marker k (from 0) FF D0 + (k & 7); interval k holds the MCUs k Ri ..
+ *         min((k + 1) Ri, M) - 1, starts on a byte boundary with the DC predictors 0, and is decoded
+ *         by a decoder of its own: the bits behind its last block are ignored
  *     16  384 bytes: the quantisation tables of Y, Cb, Cr, as in MIPX_OP_JPEGD's payload
  *    400  6 bytes: DC table index of Y, Cb, Cr, then AC table index of Y, Cb, Cr (0 or 1); 10 zeros
  *    416  four tables of 272 bytes, DC 0, DC 1, AC 0, AC 1: the DHT's 16 counts, then up to 256
@@ -262,9 +269,13 @@ enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODA
  * MIPX_JPEGH_OK: the payload holds what jpeg_read_coefficients gives for the file.
  * MIPX_JPEGH_UNSYNCED: the decoders, started at every 128th byte of the unstuffed scan, did not
  * agree on the codeword boundaries within the fixed number of launches (scans of more than 64
- * KiB almost without end-of-block codes); the caller decodes on the host instead.
- * MIPX_JPEGH_BAD: not decodable: length above the capacity; an FF that no 00 follows (a marker, a
- * restart marker, a fill byte, the last byte); code counts that sum past 256 or overflow a length;
+ * KiB almost without end-of-block codes); the caller decodes on the host instead.  Never reported
+ * for a scan of K >= 2 restart intervals, whose boundaries are its markers.
+ * MIPX_JPEGH_BAD: not decodable: length above the capacity; restart above 65535; in an ordinary
+ * scan an FF that no 00 follows (a marker, a restart marker, a fill byte, the last byte); in a scan
+ * of K >= 2 intervals an FF that neither 00 nor D0..D7 follows (the last byte included), a number
+ * of markers other than K - 1, marker k with another value than D0 + (k & 7), an interval that ends
+ * before its last block (an empty one too); code counts that sum past 256 or overflow a length;
  * a table index above 1; a code that is in no table; a run and value that pass coefficient 63; a
  * DC symbol above 15; a scan that ends before its last block; a DC outside int16.  (A run of 16
  * zeros that passes coefficient 63 ends the block, as in libjpeg.)  Bits behind the last block are

@@ -14,6 +14,8 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpegh420 --w 3840 --h 2160 --n 64 --q 75     (entropy-coded scan -> RGB)
     python scripts/op_bench.py jpeghd420 --w 3840 --h 2160 --n 64 --q 75    (the entropy decoder alone)
     python scripts/op_bench.py jpegh420 --file tests/golden/testdata/large.jpg --n 64   (a photograph's scan)
+    python scripts/op_bench.py jpeghd420 --w 3840 --h 2160 --n 64 --q 75 --restart 8    (a restart interval of 8 MCUs)
+    python scripts/op_bench.py jpeghd420 --file tests/golden/testdata/large.jpg --n 64 --restart r1   (of one MCU row)
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
          jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444 jpegrt420 jpegrt444
          jpege420 jpege444 jpegcs420 jpegcs444 jpegh420 jpegh444 jpeghd420 jpeghd444
@@ -58,6 +60,10 @@ def main():
                          "jpegrt420 / jpegrt444: the round trip's decode at 1/shrink (0 = 1)")
     ap.add_argument("--file", default="", help="jpegh* / jpeghd*: n copies of this JPEG's scan instead of the coder's "
                                                "output on noise (sets w, h and the layout)")
+    ap.add_argument("--restart", default=None,
+                    help="jpegh* / jpeghd*: n copies of one file that Pillow writes at --q of the pixels (of --file, else "
+                         "noise) with a restart interval of N MCUs, or of R MCU rows as rR; 0: the same file without "
+                         "restart markers, the twin to compare with")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -133,7 +139,27 @@ def main():
     if a.op in JPEGH:   # one input slot per image in; RGB (jpegh*) or MIPX_OP_JPEGD's payload (jpeghd*) out
         b = ob = 3
         layout = 1 if a.op.endswith("420") else 0
-        if a.file:
+        if a.restart is not None:
+            import io
+            import numpy as np
+            from PIL import Image, ImageFile
+            from imaginary_amd import codec
+            if a.file:
+                px = codec.decode(open(a.file, "rb").read())[:, :, :3]
+            else:
+                px = np.random.default_rng(1).integers(0, 256, (h, w, 3), dtype=np.uint8)
+            kw = {}
+            if a.restart.startswith("r"):
+                kw = dict(restart_marker_rows=int(a.restart[1:]))
+            elif int(a.restart):
+                kw = dict(restart_marker_blocks=int(a.restart))
+            ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 1 << 26)   # noise at a high quality is a long scan
+            out = io.BytesIO()
+            Image.fromarray(np.ascontiguousarray(px)).save(out, "JPEG", quality=a.q, subsampling=2 if layout else 0, **kw)
+            file_slot, layout = codec.jpeg_huff_slot(out.getvalue(), restart=True)
+            w, h = px.shape[1], px.shape[0]
+            ow, oh = w, h
+        elif a.file:
             from imaginary_amd import codec
             buf = open(a.file, "rb").read()
             hd = codec.header(buf)
@@ -294,6 +320,8 @@ def main():
                         statuses=sorted(set(head[:, 1].tolist())))
         if a.op in JPEGH:   # the statuses, and what a request uploads next to its RGB
             lengths = x.view(n, in_img)[:, :4].cpu().numpy().view("<u4")
+            if a.restart is not None:
+                line.update(restart=a.restart, restart_mcus=int(x.view(n, in_img)[0, 4:8].cpu().numpy().view("<u4")[0]))
             line.update(q=a.q, file=os.path.basename(a.file), capacity=in_img - 1504,
                         mean_length=round(float(lengths.mean()), 1), upload_bytes=round(1504 + float(lengths.mean()), 1),
                         rgb_bytes=w * h * 3, statuses=sorted(set(status.cpu().tolist())))
