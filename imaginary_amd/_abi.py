@@ -39,6 +39,7 @@ OP_NAMES = {OP_ROT: "rot", OP_FLIP: "flip", OP_SHRINK: "shrink", OP_REDUCE: "red
             OP_FLATTEN: "flatten", OP_BW: "bw", OP_TEXTMARK: "textmark", OP_YCC: "ycc", OP_JPEGC: "jpegc",
             OP_JPEGD: "jpegd", OP_JPEGRT: "jpegrt", OP_JPEGE: "jpege", OP_JPEGH: "jpegh"}
 JPEG_SCAN_HEADER_BYTES = 16   # MIPX_JPEG_SCAN_HEADER_BYTES: length, status, bits, 0 as little-endian uint32
+JPEG_SCAN_OPT_HEADER_BYTES = 1104   # MIPX_JPEG_SCAN_OPT_HEADER_BYTES: the same 16 (the last word 1), then four DHTs of 272
 JPEG_SCAN_OK, JPEG_SCAN_OVERFLOW, JPEG_SCAN_UNCODABLE = 0, 1, 2   # MIPX_JPEG_SCAN_*
 JPEGH_HEADER_BYTES = 1504     # MIPX_JPEGH_HEADER_BYTES: length, tables, then the file's entropy-coded scan
 JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
@@ -144,6 +145,8 @@ _SIG = {
     "mipx_plan_set_jpegc_output": (C.c_int, [C.POINTER(MipxPlan), _I, _I]),
     "mipx_jpeg_scan_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpeg_scan_output": (C.c_int, [C.POINTER(MipxPlan), _I, _I]),
+    "mipx_jpeg_scan_opt_bytes": (C.c_size_t, [_I, _I, _I]),
+    "mipx_plan_set_jpeg_scan_output_optimized": (C.c_int, [C.POINTER(MipxPlan), _I, _I]),
     "mipx_jpeg_qtables": (C.c_int, [_I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "mipx_jpegd_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegd_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
@@ -171,6 +174,8 @@ _SIG = {
     "mipx_op_rgb_to_jpegc": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P]),
     "mipx_op_jpegc_to_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, _P]),
     "mipx_op_rgb_to_jpeg_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P]),
+    "mipx_op_jpegc_to_scan_optimized": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, _P]),
+    "mipx_op_rgb_to_jpeg_scan_optimized": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P]),
     "mipx_jpegh_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegh_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
     "mipx_plan_set_jpegh_input_scaled": (C.c_int, [C.POINTER(MipxPlan), _I, _I, _I, _I]),

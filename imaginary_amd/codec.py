@@ -269,11 +269,13 @@ def _padded_planes(coefs, w: int, h: int, layout: int):
     return planes, comps, mw, mh
 
 
-def jpeg_header(w: int, h: int, layout: int, quality: int) -> bytes:
+def jpeg_header(w: int, h: int, layout: int, quality: int, tables=None) -> bytes:
     """SOI through SOS of the baseline JFIF file encode_jpeg_coefs writes: it depends on the
-    size, the sampling (YCC_444 / YCC_420) and the quality only, not on the image."""
+    size, the sampling (YCC_444 / YCC_420) and the quality only, not on the image, unless
+    `tables` (as HUFFMAN_TABLES: by DHT Tc/Th byte, (16 code counts, symbols)) replace Annex K's."""
     comps, _, _ = _jpegc_geometry(w, h, layout)
     lum, chrom = jpeg_qtables(quality)
+    tables = HUFFMAN_TABLES if tables is None else tables
 
     def seg(marker, body):
         return bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + body
@@ -287,29 +289,120 @@ def jpeg_header(w: int, h: int, layout: int, quality: int) -> bytes:
         sof += bytes([i + 1, (s << 4) | s, 0 if i == 0 else 1])
     out += seg(0xC0, sof)
     for tc in (0x00, 0x10, 0x01, 0x11):
-        out += seg(0xC4, bytes([tc]) + HUFFMAN_TABLES[tc][0] + HUFFMAN_TABLES[tc][1])
+        out += seg(0xC4, bytes([tc]) + bytes(tables[tc][0]) + bytes(tables[tc][1]))
     out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
     return bytes(out)
 
 
-def jpeg_scan_bits(coefs, w: int, h: int, layout: int):
+def _scan_symbols(coefs, w: int, h: int, layout: int):
+    """The symbols of the scan in order, with an MCU row's number: (row, Tc/Th byte of the table,
+    symbol, value): per block, dummy blocks included, the DC category of the difference; per non-zero
+    AC coefficient run << 4 | size, with 0xF0 per 16 zeros in front and 0x00 (EOB) unless coefficient
+    63 is coded.  ValueError for a value that has no code."""
+    planes, comps, mw, mh = _padded_planes(coefs, w, h, layout)
+    pred = [0, 0, 0]
+    for my in range(mh):
+        for mx in range(mw):
+            for ci, (_, _, s) in enumerate(comps):
+                t = 0 if ci == 0 else 1
+                for by in range(s):
+                    for bx in range(s):
+                        blk = planes[ci][my * s + by, mx * s + bx]
+                        d = int(blk[0]) - pred[ci]
+                        pred[ci] = int(blk[0])
+                        size = abs(d).bit_length()
+                        if size > 11:
+                            raise ValueError(f"DC difference {d}: no Annex K code past 2047")
+                        yield my, t, size, d
+                        nz = np.flatnonzero(blk[1:]) + 1
+                        prev = 0
+                        for k in nz.tolist():
+                            run = k - prev - 1
+                            while run > 15:
+                                yield my, 0x10 | t, 0xF0, 0
+                                run -= 16
+                            v = int(blk[k])
+                            size = abs(v).bit_length()
+                            if size > 10:
+                                raise ValueError(f"AC coefficient {v}: no Annex K code past 1023")
+                            yield my, 0x10 | t, (run << 4) | size, v
+                            prev = k
+                        if prev != 63:
+                            yield my, 0x10 | t, 0x00, 0
+
+
+def jpeg_symbol_counts(coefs, w: int, h: int, layout: int):
+    """The scan's symbol counts by DHT Tc/Th byte, 256 each: Y counts into tables 0x00 and 0x10,
+    Cb and Cr together into 0x01 and 0x11 (what libjpeg's optimize_coding pass gathers).
+    ValueError as jpeg_scan."""
+    counts = {tc: [0] * 256 for tc in (0x00, 0x10, 0x01, 0x11)}
+    for _, tc, sym, _ in _scan_symbols(coefs, w, h, layout):
+        counts[tc][sym] += 1
+    return counts
+
+
+def _jpeg_code_sizes(freq):
+    """libjpeg's jpeg_gen_optimal_table up to the code sizes: per symbol its length before the
+    limiting to 16 bits, 0 for a symbol that does not occur; the last entry is the reserved point's."""
+    f = [int(v) for v in freq] + [1]     # the reserved point: no code is all ones
+    if len(f) != 257 or min(f) < 0:
+        raise ValueError("256 non-negative symbol counts")
+    size, others = [0] * 257, [-1] * 257
+    while True:
+        # the least non-zero frequency, the largest index among equals (the library scans upward with <=)
+        live = [(v, -i) for i, v in enumerate(f) if v]
+        if len(live) < 2:
+            return size
+        live.sort()
+        c1, c2 = -live[0][1], -live[1][1]
+        f[c1] += f[c2]
+        f[c2] = 0
+        size[c1] += 1
+        while others[c1] >= 0:
+            c1 = others[c1]
+            size[c1] += 1
+        others[c1] = c2
+        size[c2] += 1
+        while others[c2] >= 0:
+            c2 = others[c2]
+            size[c2] += 1
+
+
+def jpeg_optimal_table(freq):
+    """The Huffman table libjpeg's optimize_coding makes of 256 symbol counts (jchuff.c
+    jpeg_gen_optimal_table, tie-breaks included; PARITY_ASSUMPTIONS.md row 24) as (16 code counts,
+    symbols), the form of HUFFMAN_TABLES' entries.  Counts that sum to 10^9 or more are outside
+    the library's search."""
+    size = _jpeg_code_sizes(freq)
+    bits = [0] * (max(max(size), 16) + 1)
+    for s in size:
+        if s:
+            bits[s] += 1
+    for i in range(len(bits) - 1, 16, -1):
+        while bits[i] > 0:
+            j = i - 2
+            while bits[j] == 0:
+                j -= 1
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    i = 16
+    while i > 0 and bits[i] == 0:
+        i -= 1
+    if i:
+        bits[i] -= 1                     # the reserved point's code
+    symbols = sorted((s for s in range(256) if size[s]), key=lambda s: (size[s], s))
+    return bytes(bits[1:17]), bytes(symbols)
+
+
+def jpeg_scan_bits(coefs, w: int, h: int, layout: int, tables=None):
     """(scan, bits): jpeg_scan's bytes, and the scan's length in bits before the last byte is
     padded and the 0xFF bytes are stuffed (what the engine's slot header reports)."""
-    planes, comps, mw, mh = _padded_planes(coefs, w, h, layout)
-    dc_codes = [_huff_codes(_HUFF_DC_LUM), _huff_codes(_HUFF_DC_CHR)]
-    ac_codes = [_huff_codes(_HUFF_AC_LUM), _huff_codes(_HUFF_AC_CHR)]
+    tables = HUFFMAN_TABLES if tables is None else tables
+    codes = {tc: _huff_codes(tables[tc]) for tc in (0x00, 0x10, 0x01, 0x11)}
     acc, nbits, total = 0, 0, 0  # the bit buffer, as one growing integer per MCU row
     scan = bytearray()
-    pred = [0, 0, 0]
-
-    def put(code, length):
-        nonlocal acc, nbits, total
-        acc = (acc << length) | code
-        nbits += length
-        total += length
-
-    def put_value(v, size):      # the `size` low bits of v, or of v - 1 when negative
-        put((v if v >= 0 else v - 1) & ((1 << size) - 1), size)
 
     def flush(final=False):
         nonlocal acc, nbits
@@ -324,65 +417,51 @@ def jpeg_scan_bits(coefs, w: int, h: int, layout: int):
             acc &= (1 << rest) - 1
             nbits = rest
 
-    for my in range(mh):
-        for mx in range(mw):
-            for ci, (_, _, s) in enumerate(comps):
-                t = 0 if ci == 0 else 1
-                for by in range(s):
-                    for bx in range(s):
-                        blk = planes[ci][my * s + by, mx * s + bx]
-                        d = int(blk[0]) - pred[ci]
-                        pred[ci] = int(blk[0])
-                        size = abs(d).bit_length()
-                        if size > 11:
-                            raise ValueError(f"DC difference {d}: no Annex K code past 2047")
-                        put(*dc_codes[t][size])
-                        if size:
-                            put_value(d, size)
-                        run = 0
-                        nz = np.flatnonzero(blk[1:]) + 1
-                        prev = 0
-                        for k in nz.tolist():
-                            run = k - prev - 1
-                            while run > 15:
-                                put(*ac_codes[t][0xF0])
-                                run -= 16
-                            v = int(blk[k])
-                            size = abs(v).bit_length()
-                            if size > 10:
-                                raise ValueError(f"AC coefficient {v}: no Annex K code past 1023")
-                            put(*ac_codes[t][(run << 4) | size])
-                            put_value(v, size)
-                            prev = k
-                        if prev != 63:
-                            put(*ac_codes[t][0x00])
-        flush()
+    row = 0
+    for my, tc, sym, v in _scan_symbols(coefs, w, h, layout):
+        if my != row:
+            flush()
+            row = my
+        code, length = codes[tc][sym]
+        size = sym & 15 if tc & 0x10 else sym
+        # the code, then the `size` low bits of v, or of v - 1 when negative
+        acc = (((acc << length) | code) << size) | ((v if v >= 0 else v - 1) & ((1 << size) - 1))
+        nbits += length + size
+        total += length + size
     flush(final=True)
     return bytes(scan), total
 
 
-def jpeg_scan(coefs, w: int, h: int, layout: int) -> bytes:
+def jpeg_scan(coefs, w: int, h: int, layout: int, tables=None) -> bytes:
     """The entropy-coded scan of the engine's quantised coefficients (MIPX_OP_JPEGC: int16, Y
     then Cb then Cr, real blocks in raster order, natural order inside a block), without EOI:
-    the Annex K Huffman tables, one interleaved scan, libjpeg's dummy blocks where the real
+    the Annex K Huffman tables (or `tables`, as jpeg_header takes them), one interleaved scan,
+    libjpeg's dummy blocks where the real
     blocks do not fill whole MCUs (zero AC; DC copied from the block to the left, or, in a
     wholly dummy block row, from the last block of the same MCU's row above), the last byte
     padded with 1-bits, every 0xFF followed by 0x00.  What a plan that ends with MIPX_OP_JPEGE
     gives (PARITY_ASSUMPTIONS.md row 21).  ValueError for a coefficient no Annex K code exists
     for: an AC magnitude above 1023 or a DC difference magnitude above 2047."""
-    return jpeg_scan_bits(coefs, w, h, layout)[0]
+    return jpeg_scan_bits(coefs, w, h, layout, tables)[0]
 
 
-def jpeg_from_scan(scan, w: int, h: int, layout: int, quality: int) -> bytes:
-    """The file: jpeg_header, the scan (jpeg_scan, or the bytes of an engine slot), EOI."""
-    return jpeg_header(w, h, layout, quality) + bytes(scan) + b"\xff\xd9"
+def jpeg_from_scan(scan, w: int, h: int, layout: int, quality: int, tables=None) -> bytes:
+    """The file: jpeg_header, the scan (jpeg_scan, or the bytes of an engine slot), EOI; `tables`
+    are the ones the scan was coded with, None for Annex K's."""
+    return jpeg_header(w, h, layout, quality, tables) + bytes(scan) + b"\xff\xd9"
 
 
-def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int) -> bytes:
+def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int, tables=None) -> bytes:
     """A baseline JFIF file from the engine's quantised coefficients (MIPX_OP_JPEGC), made at
     `quality` in `layout` (YCC_444 / YCC_420).  Stand-in for libjpeg's jpeg_write_coefficients:
-    jpeg_from_scan of jpeg_scan."""
-    return jpeg_from_scan(jpeg_scan(coefs, w, h, layout), w, h, layout, quality)
+    jpeg_from_scan of jpeg_scan.  tables: None for Annex K's, "optimal" for the ones libjpeg's
+    optimize_coding makes of the image (jpeg_optimal_table of jpeg_symbol_counts), or a dict as
+    jpeg_header takes."""
+    if isinstance(tables, str):
+        if tables != "optimal":
+            raise ValueError(f"tables {tables!r}")
+        tables = {tc: jpeg_optimal_table(f) for tc, f in jpeg_symbol_counts(coefs, w, h, layout).items()}
+    return jpeg_from_scan(jpeg_scan(coefs, w, h, layout, tables), w, h, layout, quality, tables)
 
 
 # ---- quantised coefficients from a JPEG (the engine's MIPX_OP_JPEGD input) -----------------

@@ -22,6 +22,14 @@
 //                    capacity; the header
 // Images whose verdict is not "ok" are skipped by every later kernel but for the header.
 //
+// With optimised tables (PARITY_ASSUMPTIONS.md row 24) two launches go in front, and the count and
+// pack kernels read the image's own codes from the workspace instead of the Annex K ones:
+//   k_jpege_hist     the same lanes walk their blocks once and count the symbols: a histogram of
+//                    4 tables x 256 per workgroup in LDS, then its non-zero bins into the image's by
+//                    integer atomic adds (sums do not depend on the order)
+//   k_jpege_tables   one workgroup per image, one wave per table: libjpeg's jpeg_gen_optimal_table,
+//                    the code tables into the workspace and the four DHTs into the slot's header
+//
 // The count and pack kernels stage their tile's blocks through LDS with coalesced 16-byte loads
 // (8 lanes per block), blocks 33 dwords apart, so that the lanes of a wave, each walking its own
 // block in zigzag order, read 32 different banks.  Scan order is not memory order (4:2:0
@@ -54,7 +62,11 @@ static_assert(sizeof(JpegeInfo) == 32, "JpegeWork sizes the records");
 struct JpegeArgs {
     const u8 *coefs;  // cap bytes per image
     u8 *out;          // 16 + cap bytes per image
-    const uint32_t *codes;  // build_jpege_codes
+    const uint32_t *codes;  // build_jpege_codes, or k_jpege_tables' in the workspace
+    uint32_t codes_stride;  // words between two images' codes: 0 (Annex K for all), or 4 tables' worth
+    uint32_t head;          // bytes of a slot in front of its scan
+    uint32_t *hist;         // optimised tables only: 4 x 256 symbol counts per image, in the codes' order
+    uint32_t *opt_codes;    // ... and the codes made of them
     JpegeInfo *info;
     uint32_t *stream;  // cap bytes per image
     uint32_t *counts;
@@ -173,24 +185,24 @@ __device__ __forceinline__ Lane stage_tile(const JpegeArgs &a, const u8 *coefs, 
 
 __device__ __forceinline__ uint32_t bit_length(uint32_t v) { return v ? 32u - __builtin_clz(v) : 0u; }
 
-// Codes one block (coef: its staged coefficients, natural order) into `sink` (put(bits, count),
-// count <= 27); true when a value had no code.  Such a value is coded as the largest category, so
-// that counting and packing still agree.
+// Walks one block (coef: its staged coefficients, natural order) and hands `sink` its symbols:
+// sink.dc(size, low) for the DC category, sink.ac(run << 4 | size, size, low) per coded coefficient
+// and for EOB (0, 0, 0), sink.zrl() per 0xF0; `low` are the `size` bits behind the code.  True when a
+// value had no code.  Such a value is coded as the largest category, so that counting and packing
+// still agree.
+// The walker has a coefficient's size in a register when it makes the symbol, so it hands it over:
+// a sink does not take it out of the symbol again per coefficient.
 template <class Sink>
-__device__ __forceinline__ bool code_block(const Lane &me, const int16_t *coef, const uint32_t *codes, Sink &sink) {
+__device__ __forceinline__ bool walk_block(const Lane &me, const int16_t *coef, Sink &sink) {
     bool bad = false;
-    const uint32_t *dc_codes = codes + me.chroma * 2u * kJpegeCodesPerTable, *ac_codes = dc_codes + kJpegeCodesPerTable;
     {
         const int d = me.dc - me.pred;
         uint32_t size = bit_length(static_cast<uint32_t>(d < 0 ? -d : d));
         if (size > 11u) bad = true, size = 11u;
-        const uint32_t e = dc_codes[size];
-        const uint32_t low = static_cast<uint32_t>(d < 0 ? d - 1 : d) & ((1u << size) - 1u);
-        sink.put((e & 0xffffu) << size | low, (e >> 16) + size);
+        sink.dc(size, static_cast<uint32_t>(d < 0 ? d - 1 : d) & ((1u << size) - 1u));
     }
     uint32_t run = 0;
     if (me.real) {
-        const uint32_t zrl = ac_codes[0xf0];
         for (uint32_t k0 = 1; k0 < 64u; k0 += 7u) {  // 9 groups of 7: the group's LDS reads go out together
             int group[7];
 #pragma unroll
@@ -202,38 +214,62 @@ __device__ __forceinline__ bool code_block(const Lane &me, const int16_t *coef, 
                     ++run;
                     continue;
                 }
-                for (; run > 15u; run -= 16u) sink.put(zrl & 0xffffu, zrl >> 16);
+                for (; run > 15u; run -= 16u) sink.zrl();
                 uint32_t size = bit_length(static_cast<uint32_t>(v < 0 ? -v : v));
                 if (size > 10u) bad = true, size = 10u;
-                const uint32_t e = ac_codes[run << 4 | size];
-                const uint32_t low = static_cast<uint32_t>(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
-                sink.put((e & 0xffffu) << size | low, (e >> 16) + size);
+                sink.ac(run << 4 | size, size, static_cast<uint32_t>(v < 0 ? v - 1 : v) & ((1u << size) - 1u));
                 run = 0;
             }
         }
     } else {
         run = 63;
     }
-    if (run) sink.put(ac_codes[0] & 0xffffu, ac_codes[0] >> 16);  // EOB, unless coefficient 63 is coded
+    if (run) sink.ac(0u, 0u, 0u);  // EOB, unless coefficient 63 is coded
     return bad;
 }
 
+// The three sinks.  The two that need codes take the block's pair of tables (DC, then AC) in LDS.
+struct HistSink {  // counts into the workgroup's histogram: the block's DC table, then its AC table
+    uint32_t *hist;
+    __device__ __forceinline__ void dc(uint32_t sym, uint32_t) { atomicAdd(hist + sym, 1u); }
+    __device__ __forceinline__ void ac(uint32_t sym, uint32_t, uint32_t) { atomicAdd(hist + kJpegeCodesPerTable + sym, 1u); }
+    __device__ __forceinline__ void zrl() { atomicAdd(hist + kJpegeCodesPerTable + 0xf0u, 1u); }
+};
+
 struct CountSink {
+    const uint32_t *dc_codes, *ac_codes;
+    uint32_t zrl_bits;
     uint32_t bits = 0;
-    __device__ __forceinline__ void put(uint32_t, uint32_t count) { bits += count; }
+    __device__ __forceinline__ CountSink(const uint32_t *codes)
+        : dc_codes(codes), ac_codes(codes + kJpegeCodesPerTable), zrl_bits(ac_codes[0xf0] >> 16) {}
+    __device__ __forceinline__ void dc(uint32_t sym, uint32_t) { bits += (dc_codes[sym] >> 16) + sym; }
+    __device__ __forceinline__ void ac(uint32_t sym, uint32_t size, uint32_t) { bits += (ac_codes[sym] >> 16) + size; }
+    __device__ __forceinline__ void zrl() { bits += zrl_bits; }
 };
 
 // Bits into the image's unstuffed stream from bit `at` on, most significant first.  The stream is
 // bytes; a word holds 4 of them little-endian, so a word of 32 stream bits is stored byte-swapped.
 struct PackSink {
+    const uint32_t *dc_codes, *ac_codes;
+    uint32_t zrl_code;
     uint32_t *words;
     uint32_t limit;  // words of the stream
     uint32_t wi, fill;
     unsigned long long acc;
     bool first = true;
-    __device__ __forceinline__ PackSink(uint32_t *w, uint32_t lim, unsigned long long at)
-        : words(w), limit(lim), wi(static_cast<uint32_t>(at >> 5)), fill(static_cast<uint32_t>(at) & 31u), acc(0) {}
-    __device__ __forceinline__ void put(uint32_t v, uint32_t count) {
+    __device__ __forceinline__ PackSink(const uint32_t *codes, uint32_t *w, uint32_t lim, unsigned long long at)
+        : dc_codes(codes), ac_codes(codes + kJpegeCodesPerTable), zrl_code(ac_codes[0xf0]), words(w), limit(lim),
+          wi(static_cast<uint32_t>(at >> 5)), fill(static_cast<uint32_t>(at) & 31u), acc(0) {}
+    __device__ __forceinline__ void dc(uint32_t sym, uint32_t low) {
+        const uint32_t e = dc_codes[sym];
+        put((e & 0xffffu) << sym | low, (e >> 16) + sym);
+    }
+    __device__ __forceinline__ void ac(uint32_t sym, uint32_t size, uint32_t low) {
+        const uint32_t e = ac_codes[sym];
+        put((e & 0xffffu) << size | low, (e >> 16) + size);
+    }
+    __device__ __forceinline__ void zrl() { put(zrl_code & 0xffffu, zrl_code >> 16); }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t count) {  // count <= 27
         acc = acc << count | v;
         fill += count;
         if (fill >= 32u) {
@@ -253,9 +289,152 @@ struct PackSink {
     }
 };
 
-__device__ __forceinline__ void load_codes(const JpegeArgs &a, uint32_t *codes) {
+__device__ __forceinline__ void load_codes(const JpegeArgs &a, uint32_t img, uint32_t *codes) {
+    const uint32_t *from = a.codes + static_cast<size_t>(img) * a.codes_stride;
 #pragma unroll
-    for (uint32_t i = 0; i < 4u; ++i) codes[threadIdx.x + kTile * i] = a.codes[threadIdx.x + kTile * i];
+    for (uint32_t i = 0; i < 4u; ++i) codes[threadIdx.x + kTile * i] = from[threadIdx.x + kTile * i];
+}
+
+// ---- optimised tables: the symbols' histogram, then libjpeg's jpeg_gen_optimal_table ----------
+template <int LAYOUT>
+__global__ void __launch_bounds__(kTile) k_jpege_hist(const JpegeArgs a) {
+    __shared__ uint32_t blk[kTile * kPitch];
+    __shared__ uint32_t hist[4 * kJpegeCodesPerTable];
+    __shared__ uint32_t src[kTile];
+    const uint32_t img = blockIdx.y, tile = blockIdx.x;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) hist[threadIdx.x + kTile * i] = 0u;
+    const Lane me = stage_tile<LAYOUT>(a, a.coefs + static_cast<size_t>(img) * a.cap, tile, blk, src);  // barriers
+    bool bad = false;
+    if (me.valid) {
+        HistSink sink{hist + me.chroma * 2u * kJpegeCodesPerTable};
+        bad = walk_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), sink);
+    }
+    __syncthreads();
+    uint32_t *mine = a.hist + static_cast<size_t>(img) * (4u * kJpegeCodesPerTable);
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        const uint32_t v = hist[threadIdx.x + kTile * i];
+        if (v) atomicAdd(mine + threadIdx.x + kTile * i, v);
+    }
+    if (bad) atomicOr(&a.info[img].flags, 1u);
+}
+
+constexpr uint32_t kMaxLen = 63;  // code lengths before the limiting: below 44 for counts that sum below 2^30
+constexpr unsigned long long kNoKey = ~0ull;
+
+// The two least of four keys, a1 < a2 and b1 < b2 (or kNoKey), into a1 < a2.
+__device__ __forceinline__ void least_two(unsigned long long &a1, unsigned long long &a2, unsigned long long b1,
+                                          unsigned long long b2) {
+    const unsigned long long lo = a1 < b1 ? a1 : b1, hi = a1 < b1 ? b1 : a1, rest = a2 < b2 ? a2 : b2;
+    a1 = lo, a2 = hi < rest ? hi : rest;
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int mask) {
+    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), mask), hi = __shfl_xor(static_cast<uint32_t>(v >> 32), mask);
+    return static_cast<unsigned long long>(hi) << 32 | lo;
+}
+
+// One workgroup per image, wave t on table t of the histogram (DC 0, AC 0, DC 1, AC 1).  A lane keeps
+// five of the 257 frequencies (index lane + 64 j; 256 is the reserved point) in registers with, per
+// entry, its code size and the root of the tree it is in.  A merge is one butterfly over the key
+// frequency << 9 | 256 - index, whose two least values are the library's c1 and c2 (least frequency,
+// then largest index); every entry of either tree then grows by one bit and joins c1's, which is
+// what the library's walk along its `others` chains does.  The waves run different numbers of merges
+// and meet again at the barriers behind them.
+__global__ void __launch_bounds__(kTile) k_jpege_tables(const JpegeArgs a) {
+    __shared__ uint32_t size_of[4][256];          // raw code size per symbol, 0: not in the table
+    __shared__ uint32_t bits[4][kMaxLen + 1];     // codes per length, raw and then limited
+    __shared__ uint32_t first_code[4][17], before[4][18];  // per length: its first code, and the codes shorter than it
+    __shared__ uint8_t dht[4][kJpegDhtBytes];
+    const uint32_t img = blockIdx.x, lane = threadIdx.x & 63u, t = threadIdx.x >> 6;
+    const uint32_t *freq = a.hist + static_cast<size_t>(img) * (4u * kJpegeCodesPerTable) + t * kJpegeCodesPerTable;
+    uint32_t f[5], size[5], root[5];
+#pragma unroll
+    for (uint32_t j = 0; j < 5u; ++j) {
+        const uint32_t i = lane + 64u * j;
+        f[j] = i < 256u ? freq[i] : i == 256u ? 1u : 0u;
+        size[j] = 0u, root[j] = i;
+    }
+    for (uint32_t i = lane; i <= kMaxLen; i += 64u) bits[t][i] = 0u;
+    for (uint32_t i = lane; i < kJpegDhtBytes; i += 64u) dht[t][i] = 0;
+    __syncthreads();  // the zeros are in place before any lane adds to bits[] or writes dht[]
+    for (;;) {
+        unsigned long long k1 = kNoKey, k2 = kNoKey;
+#pragma unroll
+        for (uint32_t j = 0; j < 5u; ++j) {
+            const uint32_t i = lane + 64u * j;
+            const unsigned long long k = f[j] ? static_cast<unsigned long long>(f[j]) << 9 | (256u - i) : kNoKey;
+            least_two(k1, k2, k, kNoKey);
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) least_two(k1, k2, shfl_xor64(k1, m), shfl_xor64(k2, m));
+        if (k2 == kNoKey) break;  // the same in every lane of the wave
+        const uint32_t c1 = 256u - (static_cast<uint32_t>(k1) & 511u), c2 = 256u - (static_cast<uint32_t>(k2) & 511u);
+        const uint32_t f2 = static_cast<uint32_t>(k2 >> 9);
+#pragma unroll
+        for (uint32_t j = 0; j < 5u; ++j) {
+            const uint32_t i = lane + 64u * j;
+            if (i == c1) f[j] += f2;
+            if (i == c2) f[j] = 0u;
+            if (root[j] == c1 || root[j] == c2) ++size[j], root[j] = c1;
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 5u; ++j) {
+        const uint32_t i = lane + 64u * j, s = size[j] < kMaxLen ? size[j] : kMaxLen;
+        if (i < 256u) size_of[t][i] = s;
+        if (i <= 256u && s) atomicAdd(&bits[t][s], 1u);
+    }
+    __syncthreads();
+    if (lane == 0u) {  // the library's limiting to 16 bits, and the reserved point's code dropped
+        uint32_t *b = bits[t];
+        for (uint32_t i = kMaxLen; i > 16u; --i)
+            while (b[i] > 0u) {
+                uint32_t j = i - 2u;
+                while (j > 0u && b[j] == 0u) --j;  // a shorter code exists: the lengths came from a full tree
+                if (j == 0u || b[i] < 2u) {         // not reached for counts in range; ends the loop in any case
+                    b[i] = 0u;
+                    break;
+                }
+                b[i] -= 2u, b[i - 1u] += 1u, b[j + 1u] += 2u, b[j] -= 1u;
+            }
+        uint32_t longest = 16u;
+        while (longest > 0u && b[longest] == 0u) --longest;
+        if (longest) --b[longest];
+        uint32_t code = 0u, seen = 0u;
+        for (uint32_t len = 1; len <= 16u; ++len) {  // Annex C
+            first_code[t][len] = code, before[t][len] = seen;
+            code = (code + b[len]) << 1, seen += b[len];
+            dht[t][len - 1u] = static_cast<uint8_t>(b[len]);
+        }
+        before[t][17] = seen;
+    }
+    __syncthreads();
+    // A symbol's place among the coded ones, by raw size and then by value, gives its length and code.
+    uint32_t *codes = a.opt_codes + static_cast<size_t>(img) * (4u * kJpegeCodesPerTable) + t * kJpegeCodesPerTable;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t i = lane + 64u * j, s = size_of[t][i];
+        uint32_t rank = 0u;
+        for (uint32_t k = 0; k < 256u; ++k) {
+            const uint32_t o = size_of[t][k];
+            rank += (o != 0u && (o < s || (o == s && k < i))) ? 1u : 0u;
+        }
+        uint32_t entry = 0u;
+        if (s && rank < before[t][17]) {
+            uint32_t len = 1u;
+            while (before[t][len + 1u] <= rank) ++len;  // ends: rank < before[17]
+            entry = len << 16 | (first_code[t][len] + rank - before[t][len]);
+            dht[t][16u + rank] = static_cast<uint8_t>(i);
+        }
+        codes[i] = entry;
+    }
+    __syncthreads();
+    // the slot's tables are DC 0, DC 1, AC 0, AC 1
+    u8 *to = a.out + static_cast<size_t>(img) * (static_cast<size_t>(a.head) + a.cap) + MIPX_JPEG_SCAN_HEADER_BYTES +
+             ((t & 1u) * 2u + (t >> 1)) * kJpegDhtBytes;
+    for (uint32_t i = lane; i < kJpegDhtBytes; i += 64u) to[i] = dht[t][i];
 }
 
 template <int LAYOUT>
@@ -265,12 +444,12 @@ __global__ void __launch_bounds__(kTile) k_jpege_count(const JpegeArgs a) {
     __shared__ uint32_t src[kTile];
     __shared__ uint32_t wsum[kTile / 64];
     const uint32_t img = blockIdx.y, tile = blockIdx.x;
-    load_codes(a, codes);
+    load_codes(a, img, codes);
     const Lane me = stage_tile<LAYOUT>(a, a.coefs + static_cast<size_t>(img) * a.cap, tile, blk, src);
-    CountSink sink;
+    CountSink sink(codes + me.chroma * 2u * kJpegeCodesPerTable);
     bool bad = false;
     if (me.valid) {
-        bad = code_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), codes, sink);
+        bad = walk_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), sink);
         a.counts[static_cast<size_t>(img) * a.blocks + tile * kTile + threadIdx.x] = sink.bits;
     }
     uint32_t total;
@@ -324,14 +503,15 @@ __global__ void __launch_bounds__(kTile) k_jpege_pack(const JpegeArgs a) {
     __shared__ uint32_t wsum[kTile / 64];
     const uint32_t img = blockIdx.y, tile = blockIdx.x, s = tile * kTile + threadIdx.x;
     if (a.info[img].status != MIPX_JPEG_SCAN_OK) return;  // the whole workgroup
-    load_codes(a, codes);
+    load_codes(a, img, codes);
     const Lane me = stage_tile<LAYOUT>(a, a.coefs + static_cast<size_t>(img) * a.cap, tile, blk, src);
     uint32_t total;
     const uint32_t before = block_scan(me.valid ? a.counts[static_cast<size_t>(img) * a.blocks + s] : 0u, wsum, &total);
     if (!me.valid) return;
     const unsigned long long at = a.tile_offs[static_cast<size_t>(img) * a.tiles + tile] + before;
-    PackSink sink(a.stream + static_cast<size_t>(img) * (a.cap / 4u), a.cap / 4u, at);
-    code_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), codes, sink);
+    PackSink sink(codes + me.chroma * 2u * kJpegeCodesPerTable, a.stream + static_cast<size_t>(img) * (a.cap / 4u),
+                  a.cap / 4u, at);
+    walk_block(me, reinterpret_cast<const int16_t *>(blk + threadIdx.x * kPitch), sink);
     if (s + 1u == a.blocks) {  // the scan's last block: 1-bits up to the byte
         const uint32_t pad = (8u - (static_cast<uint32_t>(a.info[img].bits) & 7u)) & 7u;
         if (pad) sink.put((1u << pad) - 1u, pad);
@@ -364,7 +544,7 @@ __global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
     __shared__ uint32_t wsum[kTile / 64];
     const uint32_t img = blockIdx.y, chunk = blockIdx.x;
     const JpegeInfo *info = a.info + img;
-    u8 *slot = a.out + static_cast<size_t>(img) * (MIPX_JPEG_SCAN_HEADER_BYTES + static_cast<size_t>(a.cap));
+    u8 *slot = a.out + static_cast<size_t>(img) * (static_cast<size_t>(a.head) + a.cap);
     const uint32_t status = info->status;
     const unsigned long long bits = info->bits, bytes = (bits + 7ull) >> 3;
     if (chunk == 0 && threadIdx.x == 0) {
@@ -375,7 +555,7 @@ __global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
         hdr.x = length > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(length);
         hdr.y = status;
         hdr.z = bits > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(bits);
-        hdr.w = 0u;
+        hdr.w = a.head == MIPX_JPEG_SCAN_HEADER_BYTES ? 0u : 1u;  // 1: the four tables follow
         __builtin_memcpy(slot, &hdr, 16);  // any alignment: one global_store_dwordx4
     }
     if (status != MIPX_JPEG_SCAN_OK || static_cast<unsigned long long>(chunk) * kChunk >= bytes) return;
@@ -384,7 +564,7 @@ __global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
     uint32_t total;
     const uint32_t before = block_scan(ff_bytes(word, first, bytes), wsum, &total);
     unsigned long long pos = first + a.chunk_offs[static_cast<size_t>(img) * a.chunks + chunk] + before;
-    u8 *data = slot + MIPX_JPEG_SCAN_HEADER_BYTES;
+    u8 *data = slot + a.head;
 #pragma unroll
     for (uint32_t j = 0; j < 4u; ++j) {
         if (first + j >= bytes) break;
@@ -400,12 +580,17 @@ __global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
 
 }  // namespace
 
-int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, u8 *work, hipStream_t st) {
-    const JpegeWork W(n, w, h);
+int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, bool optimise, u8 *work,
+                 hipStream_t st) {
+    const JpegeWork W(n, w, h, optimise);
     const bool sub = layout == MIPX_YCC_420;
     JpegeArgs a;
     a.coefs = d_coefs, a.out = d_out;
-    a.codes = device_jpege_codes();
+    a.hist = reinterpret_cast<uint32_t *>(work + W.hist);
+    a.opt_codes = reinterpret_cast<uint32_t *>(work + W.opt_codes);
+    a.codes = optimise ? a.opt_codes : device_jpege_codes();
+    a.codes_stride = optimise ? 4u * kJpegeCodesPerTable : 0u;
+    a.head = optimise ? MIPX_JPEG_SCAN_OPT_HEADER_BYTES : MIPX_JPEG_SCAN_HEADER_BYTES;
     if (!a.codes) {
         set_error("jpeg coefficients to scan: no Huffman code table on the device");
         return MIPX_EDEVICE;
@@ -432,6 +617,14 @@ int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, 
     MIPX_HIP(hipMemsetAsync(work + W.info, 0, (W.stream - W.info) + static_cast<size_t>(n) * a.cap, st));
     const dim3 threads(kTile), by_tile(a.tiles, n), by_chunk(a.chunks, n), by_image(n);
     int e;
+    if (optimise) {
+        MIPX_HIP(hipMemsetAsync(a.hist, 0, static_cast<size_t>(n) * 4u * kJpegeCodesPerTable * sizeof(uint32_t), st));
+        if (sub) hipLaunchKernelGGL(k_jpege_hist<MIPX_YCC_420>, by_tile, threads, 0, st, a);
+        else hipLaunchKernelGGL(k_jpege_hist<MIPX_YCC_444>, by_tile, threads, 0, st, a);
+        if ((e = launch_check("k_jpege_hist"))) return e;
+        hipLaunchKernelGGL(k_jpege_tables, by_image, threads, 0, st, a);
+        if ((e = launch_check("k_jpege_tables"))) return e;
+    }
     if (sub) hipLaunchKernelGGL(k_jpege_count<MIPX_YCC_420>, by_tile, threads, 0, st, a);
     else hipLaunchKernelGGL(k_jpege_count<MIPX_YCC_444>, by_tile, threads, 0, st, a);
     if ((e = launch_check("k_jpege_count"))) return e;

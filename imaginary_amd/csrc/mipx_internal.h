@@ -213,8 +213,11 @@ int jpegds_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int l
 int jpegrt_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, int quality, int shrink,
                   hipStream_t st);
 // k_jpege.hip: the coefficients k_jpegc writes -> one output slot per image (mipx_jpeg_scan_bytes): the
-// Huffman-coded, padded and stuffed scan behind a 16-byte header.  work: a JpegeWork of (n, w, h), 16-byte aligned
-int jpege_launch(const uint8_t *coefs, uint8_t *out, int n, int w, int h, int layout, uint8_t *work, hipStream_t st);
+// Huffman-coded, padded and stuffed scan behind a 16-byte header; with `optimise` coded with the image's own
+// tables (row 24), which stand behind the header (mipx_jpeg_scan_opt_bytes).  work: a JpegeWork of
+// (n, w, h, optimise), 16-byte aligned
+int jpege_launch(const uint8_t *coefs, uint8_t *out, int n, int w, int h, int layout, bool optimise, uint8_t *work,
+                 hipStream_t st);
 // The coder's workspace, sized without the layout (both fit): byte offsets of its parts, each a multiple
 // of 256, and the total.  Per image: cap = 384 ceil(w / 8) ceil(h / 8) bytes, the 4:4:4 coefficients;
 // blocks = the scan's blocks, dummy ones included, of whichever layout has more.
@@ -230,8 +233,10 @@ struct JpegeWork {
     size_t tile_offs;
     size_t chunk_sums;  // n * chunks u32, then their exclusive scan as u64
     size_t chunk_offs;
+    size_t hist;       // optimised tables only: n * 4 * 256 u32 symbol counts, then as many codes
+    size_t opt_codes;
     size_t total;
-    JpegeWork(int n, int w, int h) {
+    JpegeWork(int n, int w, int h, bool optimise = false) {
         auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
         const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
         const size_t mcus = ((ywb + 1) / 2) * ((yhb + 1) / 2), N = static_cast<size_t>(n);
@@ -247,7 +252,9 @@ struct JpegeWork {
         tile_offs = tile_sums + up(N * tiles * 4);
         chunk_sums = tile_offs + up(N * tiles * 8);
         chunk_offs = chunk_sums + up(N * chunks * 4);
-        total = chunk_offs + up(N * chunks * 8);
+        hist = chunk_offs + up(N * chunks * 8);
+        opt_codes = hist + (optimise ? N * 4096 : 0);
+        total = opt_codes + (optimise ? N * 4096 : 0);
     }
 };
 // k_jpegh.hip: n input slots (mipx_jpegh_bytes: header, Huffman tables, the file's entropy-coded scan) ->
@@ -324,6 +331,8 @@ size_t plan_input_bytes(const mipx_plan *p);
 // bytes per image of the plan's output buffer: out_w * out_h * out_bands, or the coefficients
 // when the last step is MIPX_OP_JPEGC, or the scan's slot when it is MIPX_OP_JPEGE (plan already validated)
 size_t plan_output_bytes(const mipx_plan *p);
+// whether a w x h scan is inside the optimised tables' rule: 64 x its blocks < 10^9
+bool jpeg_opt_in_range(int w, int h, int layout);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

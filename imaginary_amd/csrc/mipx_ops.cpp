@@ -31,8 +31,9 @@ size_t op_workspace_bytes(int op, int n, int w, int h, int bands, double p0, dou
             return align_up(static_cast<size_t>(n) * ((w + s - 1) / s) * ((h + s - 1) / s) * 3);
         }
         // the entropy coder's: the coefficients, the scan before stuffing, the per-block and
-        // per-tile bit counts and their scans (JpegeWork); sized without the layout
-        case MIPX_OP_JPEGE: return JpegeWork(n, w, h).total;
+        // per-tile bit counts and their scans (JpegeWork); sized without the layout.  p0 = 1: with
+        // optimised tables, the symbol counts and the codes per image too
+        case MIPX_OP_JPEGE: return JpegeWork(n, w, h, p0 == 1.0).total;
         // the entropy decoder's: the unstuffed scans, the decoders' states and block counts, the DC
         // differences, and what the coefficient step behind it needs (JpeghWork); sized without the layout
         case MIPX_OP_JPEGH: return JpeghWork(n, w, h).total;
@@ -168,40 +169,64 @@ int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
     return jpegc_launch(d_in, d_out, n, w, h, layout, quality, as_stream(stream));
 }
 
-int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
-                          void *d_work, void *stream) {
-    if (!d_coefs || !d_out || !d_work || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
+// The checks the four entropy-coder calls share.
+static int jpege_check(const char *what, const void *d_in, const void *d_out, const void *d_work, int32_t n, int32_t w,
+                       int32_t h, int32_t layout, bool optimise) {
+    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
         return MIPX_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_work) & 15u) {
-        set_error("jpeg coefficients to scan: the workspace is not 16-byte aligned");
+        set_error("%s: the workspace is not 16-byte aligned", what);
         return MIPX_EINVAL;
     }
     // byte offsets inside an image are 32-bit in the kernels
     if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
-        set_error("jpeg coefficients to scan: image %dx%d too large (an image's bytes >= 2^32)", w, h);
+        set_error("%s: image %dx%d too large (an image's bytes >= 2^32)", what, w, h);
         return MIPX_EUNSUPPORTED;
     }
-    return jpege_launch(d_coefs, d_out, n, w, h, layout, static_cast<uint8_t *>(d_work), as_stream(stream));
+    if (optimise && !jpeg_opt_in_range(w, h, layout)) {
+        set_error("%s: a %dx%d scan has 10^9 / 64 blocks or more", what, w, h);
+        return MIPX_EINVAL;
+    }
+    return MIPX_OK;
+}
+
+static int jpegc_to_scan(const char *what, const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                         int32_t layout, bool optimise, void *d_work, void *stream) {
+    const int e = jpege_check(what, d_coefs, d_out, d_work, n, w, h, layout, optimise);
+    if (e) return e;
+    return jpege_launch(d_coefs, d_out, n, w, h, layout, optimise, static_cast<uint8_t *>(d_work), as_stream(stream));
+}
+
+static int rgb_to_jpeg_scan(const char *what, const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                            int32_t layout, int32_t quality, bool optimise, void *d_work, void *stream) {
+    if (quality < 1 || quality > 100) return MIPX_EINVAL;
+    int e = jpege_check(what, d_in, d_out, d_work, n, w, h, layout, optimise);
+    if (e) return e;
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint8_t *coefs = work + JpegeWork(n, w, h, optimise).coefs;  // packed as mipx_jpegc_bytes per image
+    e = jpegc_launch(d_in, coefs, n, w, h, layout, quality, as_stream(stream));
+    if (e) return e;
+    return jpege_launch(coefs, d_out, n, w, h, layout, optimise, work, as_stream(stream));
+}
+
+int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
+                          void *d_work, void *stream) {
+    return jpegc_to_scan("jpeg coefficients to scan", d_coefs, d_out, n, w, h, layout, false, d_work, stream);
+}
+
+int mipx_op_jpegc_to_scan_optimized(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                    int32_t layout, void *d_work, void *stream) {
+    return jpegc_to_scan("jpeg coefficients to optimised scan", d_coefs, d_out, n, w, h, layout, true, d_work, stream);
 }
 
 int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                              int32_t quality, void *d_work, void *stream) {
-    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
-        quality < 1 || quality > 100)
-        return MIPX_EINVAL;
-    if (reinterpret_cast<uintptr_t>(d_work) & 15u) {
-        set_error("rgb to jpeg scan: the workspace is not 16-byte aligned");
-        return MIPX_EINVAL;
-    }
-    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
-        set_error("rgb to jpeg scan: image %dx%d too large (an image's bytes >= 2^32)", w, h);
-        return MIPX_EUNSUPPORTED;
-    }
-    uint8_t *work = static_cast<uint8_t *>(d_work);
-    uint8_t *coefs = work + JpegeWork(n, w, h).coefs;  // packed as mipx_jpegc_bytes per image
-    const int e = jpegc_launch(d_in, coefs, n, w, h, layout, quality, as_stream(stream));
-    if (e) return e;
-    return jpege_launch(coefs, d_out, n, w, h, layout, work, as_stream(stream));
+    return rgb_to_jpeg_scan("rgb to jpeg scan", d_in, d_out, n, w, h, layout, quality, false, d_work, stream);
+}
+
+int mipx_op_rgb_to_jpeg_scan_optimized(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                       int32_t layout, int32_t quality, void *d_work, void *stream) {
+    return rgb_to_jpeg_scan("rgb to optimised jpeg scan", d_in, d_out, n, w, h, layout, quality, true, d_work, stream);
 }
 
 // The checks the three entropy-decoder calls share; *work: the workspace.

@@ -676,6 +676,19 @@ extern "C" size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout) {
     return coefs ? MIPX_JPEG_SCAN_HEADER_BYTES + coefs : 0;
 }
 
+extern "C" size_t mipx_jpeg_scan_opt_bytes(int32_t w, int32_t h, int32_t layout) {
+    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
+    return coefs ? MIPX_JPEG_SCAN_OPT_HEADER_BYTES + coefs : 0;
+}
+
+// libjpeg's search for the least frequency starts at 10^9: a scan that could count that many symbols
+// into one table (64 per block at most) is outside the optimised tables' rule
+bool mipx::jpeg_opt_in_range(int w, int h, int layout) {
+    const unsigned long long ywb = (static_cast<unsigned long long>(w) + 7) / 8, yhb = (static_cast<unsigned long long>(h) + 7) / 8;
+    const unsigned long long blocks = layout == MIPX_YCC_420 ? 6 * ((ywb + 1) / 2) * ((yhb + 1) / 2) : 3 * ywb * yhb;
+    return 64ull * blocks < 1000000000ull;
+}
+
 extern "C" size_t mipx_jpegh_bytes(int32_t w, int32_t h, int32_t layout) {
     const size_t coefs = mipx_jpegc_bytes(w, h, layout);
     return coefs ? MIPX_JPEGH_HEADER_BYTES + coefs : 0;
@@ -690,8 +703,10 @@ static bool ends_with_jpeg_output(const mipx_plan *p) {
 size_t mipx::plan_output_bytes(const mipx_plan *p) {
     if (p->n_steps > 0 && p->steps[p->n_steps - 1].op == MIPX_OP_JPEGC)
         return mipx_jpegc_bytes(p->out_w, p->out_h, p->steps[p->n_steps - 1].a[0]);
-    if (p->n_steps > 0 && p->steps[p->n_steps - 1].op == MIPX_OP_JPEGE)
-        return mipx_jpeg_scan_bytes(p->out_w, p->out_h, p->steps[p->n_steps - 1].a[0]);
+    if (p->n_steps > 0 && p->steps[p->n_steps - 1].op == MIPX_OP_JPEGE) {
+        const mipx_step &s = p->steps[p->n_steps - 1];
+        return s.a[2] ? mipx_jpeg_scan_opt_bytes(p->out_w, p->out_h, s.a[0]) : mipx_jpeg_scan_bytes(p->out_w, p->out_h, s.a[0]);
+    }
     return static_cast<size_t>(p->out_w) * p->out_h * p->out_bands;
 }
 
@@ -727,8 +742,7 @@ extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32
 }
 
 // ---- entropy-coded JPEG output (MIPX_OP_JPEGE) -----------------------------------------
-extern "C" int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, int32_t quality) {
-    const char *who = "mipx_plan_set_jpeg_scan_output";
+static int set_jpeg_scan_output(const char *who, mipx_plan *plan, int32_t layout, int32_t quality, bool optimise) {
     if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
     if (quality < 1 || quality > 100) {
         mipx::set_error("%s: quality %d outside 1..100", who, quality);
@@ -743,6 +757,10 @@ extern "C" int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, i
         mipx::set_error("%s: the plan already gives coefficients or a scan", who);
         return MIPX_EINVAL;
     }
+    if (optimise && !mipx::jpeg_opt_in_range(plan->out_w, plan->out_h, layout)) {
+        mipx::set_error("%s: a %dx%d scan has 10^9 / 64 blocks or more", who, plan->out_w, plan->out_h);
+        return MIPX_EINVAL;
+    }
     if (plan->n_steps >= MIPX_MAX_STEPS) {
         mipx::set_error("%s: the plan is full (MIPX_MAX_STEPS)", who);
         return MIPX_EINVAL;
@@ -750,9 +768,17 @@ extern "C" int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, i
     mipx_step &s = plan->steps[plan->n_steps++];
     std::memset(&s, 0, sizeof(s));
     s.op = MIPX_OP_JPEGE;
-    s.a[0] = layout, s.a[1] = quality;
+    s.a[0] = layout, s.a[1] = quality, s.a[2] = optimise ? 1 : 0;
     s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
     return MIPX_OK;
+}
+
+extern "C" int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, int32_t quality) {
+    return set_jpeg_scan_output("mipx_plan_set_jpeg_scan_output", plan, layout, quality, false);
+}
+
+extern "C" int mipx_plan_set_jpeg_scan_output_optimized(mipx_plan *plan, int32_t layout, int32_t quality) {
+    return set_jpeg_scan_output("mipx_plan_set_jpeg_scan_output_optimized", plan, layout, quality, true);
 }
 
 // ---- JPEG round trip (MIPX_OP_JPEGRT) ------------------------------------------------

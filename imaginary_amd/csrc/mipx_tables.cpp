@@ -435,4 +435,60 @@ HostTable build_jpege_codes() {
     return r;
 }
 
+int jpeg_optimal_table(const uint32_t freq[256], uint8_t dht[kJpegDhtBytes], uint32_t codes[kJpegeCodesPerTable]) {
+    constexpr int kMaxLen = 63;  // lengths past it would need counts that sum past 2^30
+    uint64_t f[257];
+    int codesize[257], others[257], bits[kMaxLen + 1];
+    for (int i = 0; i < 256; ++i) f[i] = freq[i];
+    f[256] = 1;  // the reserved point: no code is all ones
+    for (int i = 0; i <= 256; ++i) codesize[i] = 0, others[i] = -1;
+    for (int i = 0; i <= kMaxLen; ++i) bits[i] = 0;
+    std::memset(dht, 0, kJpegDhtBytes);
+    for (int i = 0; i < kJpegeCodesPerTable; ++i) codes[i] = 0;
+    for (;;) {
+        int c1 = -1, c2 = -1;  // the least frequency, the largest index among equals; then again without c1
+        for (int i = 0; i <= 256; ++i)
+            if (f[i] && (c1 < 0 || f[i] <= f[c1])) c1 = i;
+        for (int i = 0; i <= 256; ++i)
+            if (f[i] && i != c1 && (c2 < 0 || f[i] <= f[c2])) c2 = i;
+        if (c2 < 0) break;
+        f[c1] += f[c2], f[c2] = 0;
+        for (++codesize[c1]; others[c1] >= 0; ++codesize[c1]) c1 = others[c1];
+        others[c1] = c2;
+        for (++codesize[c2]; others[c2] >= 0; ++codesize[c2]) c2 = others[c2];
+    }
+    int raw = 0;
+    for (int i = 0; i <= 256; ++i) {
+        if (!codesize[i]) continue;
+        if (codesize[i] > kMaxLen) codesize[i] = kMaxLen;
+        ++bits[codesize[i]];
+        if (codesize[i] > raw) raw = codesize[i];
+    }
+    for (int i = kMaxLen; i > 16; --i)
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (j > 0 && bits[j] == 0) --j;
+            if (j == 0 || bits[i] < 2) {  // not reached for counts in range
+                bits[i] = 0;
+                break;
+            }
+            bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
+        }
+    int longest = 16;
+    while (longest > 0 && bits[longest] == 0) --longest;
+    if (longest) --bits[longest];  // the reserved point's code
+    for (int len = 1; len <= 16; ++len) dht[len - 1] = static_cast<uint8_t>(bits[len]);
+    int p = 0;
+    for (int len = 1; len <= kMaxLen; ++len)  // by raw length, then by value
+        for (int i = 0; i < 256; ++i)
+            if (codesize[i] == len && p < 256) dht[16 + p++] = static_cast<uint8_t>(i);
+    uint32_t code = 0;
+    int k = 0;
+    for (uint32_t len = 1; len <= 16; ++len) {  // Annex C
+        for (int c = 0; c < bits[len] && k < p; ++c) codes[dht[16 + k++]] = len << 16 | code++;
+        code <<= 1;
+    }
+    return raw;
+}
+
 }  // namespace mipx

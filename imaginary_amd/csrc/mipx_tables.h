@@ -75,5 +75,12 @@ HostTable build_jpegc_recips(int quality);
 // category 0..11, or an AC run << 4 | size), each length << 16 | code; 0 where the table has no code
 constexpr int kJpegeCodesPerTable = 256;
 HostTable build_jpege_codes();
+// One optimised Huffman table (libjpeg jchuff.c jpeg_gen_optimal_table, PARITY_ASSUMPTIONS.md row 24)
+// of the counts of its 256 symbols: the DHT as the engine's slots hold it (16 code counts per length,
+// then the symbols by code, zero-padded) and the codes in build_jpege_codes' format.  The serial
+// form k_jpege_tables is held to.  Returns the longest code length before the limiting to 16 bits
+// (0 for a table of no symbol).  Counts that sum to 2^30 or more are outside the rule.
+constexpr int kJpegDhtBytes = 272;
+int jpeg_optimal_table(const uint32_t freq[256], uint8_t dht[kJpegDhtBytes], uint32_t codes[kJpegeCodesPerTable]);
 
 }  // namespace mipx

@@ -12,7 +12,7 @@ import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
                    EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, OP_JPEGH, YCC_444, YCC_420,
-                   JPEG_SCAN_HEADER_BYTES, JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD, sync_tuning)
+                   JPEG_SCAN_HEADER_BYTES, JPEG_SCAN_OPT_HEADER_BYTES, JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
@@ -20,7 +20,7 @@ __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
-           "plan_set_jpeg_scan_output", "jpeg_scan_bytes", "rgb_to_jpeg_scan", "jpegc_to_scan", "scan_slot",
+           "plan_set_jpeg_scan_output", "jpeg_scan_bytes", "jpeg_scan_opt_bytes", "rgb_to_jpeg_scan", "jpegc_to_scan", "scan_slot",
            "jpegh_bytes", "plan_set_jpegh_input", "plan_set_jpegh_input_scaled", "execute_status", "jpegh_to_jpegd", "jpegh_to_rgb", "jpegh_to_rgb_scaled", "JPEGH_OK", "JPEGH_UNSYNCED", "JPEGH_BAD",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
@@ -407,11 +407,21 @@ def jpeg_scan_bytes(w: int, h: int, layout: int) -> int:
     return int(lib.mipx_jpeg_scan_bytes(w, h, layout))
 
 
-def plan_set_jpeg_scan_output(plan: MipxPlan, layout: int, quality: int) -> MipxPlan:
+def jpeg_scan_opt_bytes(w: int, h: int, layout: int) -> int:
+    """mipx_jpeg_scan_opt_bytes: bytes of one image's output slot with optimised Huffman tables."""
+    return int(lib.mipx_jpeg_scan_opt_bytes(w, h, layout))
+
+
+def plan_set_jpeg_scan_output(plan: MipxPlan, layout: int, quality: int, optimize: bool = False) -> MipxPlan:
     """mipx_plan_set_jpeg_scan_output on `plan` (in place; returned for convenience): the plan then
     gives the finished entropy-coded scan of its 3-band result (YCC_444 or YCC_420, made at
-    `quality`), one slot per image (scan_slot reads it), instead of RGB pixels."""
-    check(lib.mipx_plan_set_jpeg_scan_output(C.byref(plan), layout, quality), "mipx_plan_set_jpeg_scan_output")
+    `quality`), one slot per image (scan_slot reads it), instead of RGB pixels.  optimize: coded with
+    the image's own Huffman tables, which the slot then carries (mipx_plan_set_jpeg_scan_output_optimized)."""
+    if optimize:
+        check(lib.mipx_plan_set_jpeg_scan_output_optimized(C.byref(plan), layout, quality),
+              "mipx_plan_set_jpeg_scan_output_optimized")
+    else:
+        check(lib.mipx_plan_set_jpeg_scan_output(C.byref(plan), layout, quality), "mipx_plan_set_jpeg_scan_output")
     return plan
 
 
@@ -421,17 +431,36 @@ def _jpege_layout(plan: MipxPlan):
     return last.a[0] if last is not None and last.op == OP_JPEGE else None
 
 
-def scan_slot(slot):
+def _jpege_slot_bytes(plan: MipxPlan):
+    """Bytes of one output slot of a plan that gives scans, with or without its tables."""
+    last = plan.steps[plan.n_steps - 1]
+    return (jpeg_scan_opt_bytes if last.a[2] else jpeg_scan_bytes)(plan.out_w, plan.out_h, last.a[0])
+
+
+def scan_slot(slot, tables: bool = False):
     """(status, bits, scan) of one output slot of MIPX_OP_JPEGE (uint8, jpeg_scan_bytes long):
     scan is the `length` bytes behind the header, empty unless status is 0 (codec.jpeg_from_scan
-    makes the file of it)."""
+    makes the file of it).  With `tables`, (status, bits, scan, tables): for a slot with optimised
+    Huffman tables (jpeg_scan_opt_bytes long; the header's last word says which it is) the four it
+    carries as codec.jpeg_header takes them, by DHT Tc/Th byte; None for an Annex K slot or a
+    status other than 0."""
     slot = np.ascontiguousarray(slot, dtype=np.uint8).ravel()
-    length, status, bits, _ = (int(v) for v in slot[:JPEG_SCAN_HEADER_BYTES].view("<u4"))
+    length, status, bits, kind = (int(v) for v in slot[:JPEG_SCAN_HEADER_BYTES].view("<u4"))
+    head = JPEG_SCAN_OPT_HEADER_BYTES if kind == 1 else JPEG_SCAN_HEADER_BYTES
     if status != 0:
-        return status, bits, b""
-    if length > slot.size - JPEG_SCAN_HEADER_BYTES:
+        return (status, bits, b"", None) if tables else (status, bits, b"")
+    if slot.size < head or length > slot.size - head:
         raise ValueError(f"slot of {slot.size} bytes says its scan has {length}")
-    return status, bits, slot[JPEG_SCAN_HEADER_BYTES:JPEG_SCAN_HEADER_BYTES + length].tobytes()
+    scan = slot[head:head + length].tobytes()
+    if not tables:
+        return status, bits, scan
+    found = None
+    if kind == 1:
+        found = {}
+        for k, tc in enumerate((0x00, 0x01, 0x10, 0x11)):   # DC 0, DC 1, AC 0, AC 1
+            t = slot[JPEG_SCAN_HEADER_BYTES + 272 * k:JPEG_SCAN_HEADER_BYTES + 272 * (k + 1)]
+            found[tc] = (t[:16].tobytes(), t[16:16 + int(t[:16].sum())].tobytes())
+    return status, bits, scan, found
 
 
 def fit_dimension(iw, ih, fw, fh):
@@ -491,7 +520,7 @@ class Engine:
         if coefs is not None:  # the coefficients of one image, described as the plan's w x h x 3
             shape, dtype = (jpegc_bytes(plan.out_w, plan.out_h, coefs) // 2,), np.int16
         elif scan is not None:  # ... or its slot
-            shape, dtype = (jpeg_scan_bytes(plan.out_w, plan.out_h, scan),), np.uint8
+            shape, dtype = (_jpege_slot_bytes(plan),), np.uint8
         else:
             shape, dtype = (plan.out_h, plan.out_w, plan.out_bands), np.uint8
         if out is None:
@@ -682,28 +711,30 @@ def rgb_to_jpegc(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
     return dout.download((n, need // 2), np.int16)
 
 
-def rgb_to_jpeg_scan(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
+def rgb_to_jpeg_scan(imgs: np.ndarray, layout: int, quality: int, optimize: bool = False) -> np.ndarray:
     """mipx_op_rgb_to_jpeg_scan on (h, w, 3) or (n, h, w, 3) uint8; returns the slots,
-    (n, jpeg_scan_bytes) uint8."""
+    (n, jpeg_scan_bytes) uint8; with `optimize` mipx_op_rgb_to_jpeg_scan_optimized and
+    (n, jpeg_scan_opt_bytes)."""
     sync_tuning()
     x = _batch(imgs)
     n, h, w, b = x.shape
-    need = jpeg_scan_bytes(w, h, layout)
+    need = (jpeg_scan_opt_bytes if optimize else jpeg_scan_bytes)(w, h, layout)
     if b != 3 or need == 0:
         raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
-    what = "mipx_op_rgb_to_jpeg_scan"
+    what = "mipx_op_rgb_to_jpeg_scan_optimized" if optimize else "mipx_op_rgb_to_jpeg_scan"
     din = _dev("in", what, x.nbytes, w * 3, x)
     dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
-    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 0.0, 0.0))
-    check(lib.mipx_op_rgb_to_jpeg_scan(din.ptr, dout.ptr, n, w, h, layout, quality, ws.ptr, None), what)
+    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 1.0 if optimize else 0.0, 0.0))
+    check(getattr(lib, what)(din.ptr, dout.ptr, n, w, h, layout, quality, ws.ptr, None), what)
     synchronize()
     _check_guards(what, din, dout, ws)
     return dout.download((n, need))
 
 
-def jpegc_to_scan(coefs: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
+def jpegc_to_scan(coefs: np.ndarray, w: int, h: int, layout: int, optimize: bool = False) -> np.ndarray:
     """mipx_op_jpegc_to_scan on coefficients as rgb_to_jpegc returns them, (jpegc_bytes / 2,) or
-    (n, jpegc_bytes / 2) int16; returns the slots, (n, jpeg_scan_bytes) uint8."""
+    (n, jpegc_bytes / 2) int16; returns the slots, (n, jpeg_scan_bytes) uint8; with `optimize`
+    mipx_op_jpegc_to_scan_optimized and (n, jpeg_scan_opt_bytes)."""
     sync_tuning()
     x = np.ascontiguousarray(coefs, dtype=np.int16)
     if x.ndim == 1:
@@ -711,12 +742,12 @@ def jpegc_to_scan(coefs: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
     have = jpegc_bytes(w, h, layout)
     if x.ndim != 2 or have == 0 or x.shape[1] * 2 != have:
         raise ValueError(f"coefficients of shape {np.shape(coefs)} for {w}x{h} layout {layout}: {have // 2} per image")
-    n, need = x.shape[0], jpeg_scan_bytes(w, h, layout)
-    what = "mipx_op_jpegc_to_scan"
+    n, need = x.shape[0], (jpeg_scan_opt_bytes if optimize else jpeg_scan_bytes)(w, h, layout)
+    what = "mipx_op_jpegc_to_scan_optimized" if optimize else "mipx_op_jpegc_to_scan"
     din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x.view(np.uint8))
     dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
-    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 0.0, 0.0))
-    check(lib.mipx_op_jpegc_to_scan(din.ptr, dout.ptr, n, w, h, layout, ws.ptr, None), what)
+    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 1.0 if optimize else 0.0, 0.0))
+    check(getattr(lib, what)(din.ptr, dout.ptr, n, w, h, layout, ws.ptr, None), what)
     synchronize()
     _check_guards(what, din, dout, ws)
     return dout.download((n, need))
@@ -885,7 +916,7 @@ def execute(plan: MipxPlan, imgs: np.ndarray, wm: Optional[np.ndarray] = None,
     scan = _jpege_layout(plan)
     out1 = jpegc_bytes(plan.out_w, plan.out_h, coefs) if coefs is not None else plan.out_w * plan.out_h * plan.out_bands
     if scan is not None:
-        out1 = jpeg_scan_bytes(plan.out_w, plan.out_h, scan)
+        out1 = _jpege_slot_bytes(plan)
     dout = _dev("out", what, n * out1, plan.out_w * plan.out_bands)
     wsb = lib.mipx_workspace_bytes(C.byref(plan), n)
     ws = _dev("ws", what, wsb) if wsb else None

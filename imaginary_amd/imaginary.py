@@ -510,12 +510,13 @@ class JpegScan:
     h: int
     layout: int
     quality: int
+    tables: Optional[dict] = None   # the Huffman tables the scan is coded with (jpeg_optimize); None: Annex K's
 
 
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
             text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None,
             jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False, jpeg_scan: bool = False,
-            jpeg_huff: Optional[tuple] = None):
+            jpeg_huff: Optional[tuple] = None, jpeg_optimize: bool = False):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -544,7 +545,10 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     (4:2:0 below Q 90, 4:4:4 from Q 90, as codec.encode samples) and a JpegCoefs is returned;
     results of other band counts come back as pixels.  With `jpeg_scan` too, the plan ends with the
     entropy-coding step instead and a JpegScan is returned; a slot that reports an overflow or an
-    uncodable coefficient makes the request run again with the coefficient step."""
+    uncodable coefficient makes the request run again with the coefficient step.  With
+    `jpeg_optimize` besides `jpeg_scan`, the scan is coded with the image's own optimised Huffman
+    tables (libjpeg's optimize_coding) and the JpegScan carries them; a result too large for that
+    step (10^9 / 64 scan blocks or more) goes to the coefficient step like a slot that is not OK."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         return process_bytes(bytes(img), opts, wm, text)
     if isinstance(img, _Staged):
@@ -597,10 +601,20 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
             if jpeg_scan:
                 coded = _abi.MipxPlan()
                 C.memmove(C.byref(coded), C.byref(plan), C.sizeof(plan))
-                plan_set_jpeg_scan_output(coded, layout, jpeg_quality)
-                status, _, scan = scan_slot(_run(coded, px, wm))
+                status = None
+                if jpeg_optimize:
+                    try:
+                        plan_set_jpeg_scan_output(coded, layout, jpeg_quality, True)
+                    except _abi.MipxError as e:   # a scan of 10^9 / 64 blocks or more: like a slot that is not OK
+                        if e.code != _abi.MIPX_EINVAL:
+                            raise
+                    else:
+                        status, _, scan, tables = scan_slot(_run(coded, px, wm), tables=True)
+                else:
+                    plan_set_jpeg_scan_output(coded, layout, jpeg_quality)
+                    (status, _, scan), tables = scan_slot(_run(coded, px, wm)), None
                 if status == _abi.JPEG_SCAN_OK:
-                    return JpegScan(scan, plan.out_w, plan.out_h, layout, jpeg_quality)
+                    return JpegScan(scan, plan.out_w, plan.out_h, layout, jpeg_quality, tables)
             plan_set_jpegc_output(plan, layout, jpeg_quality)
             return JpegCoefs(_run(plan, px, wm), plan.out_w, plan.out_h, layout, jpeg_quality)
         return _run(plan, px, wm)
@@ -613,7 +627,7 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
                   jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False,
-                  jpeg_huff: bool = False, jpeg_huff_restart: bool = False) -> Image:
+                  jpeg_huff: bool = False, jpeg_huff_restart: bool = False, jpeg_optimize: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -627,6 +641,10 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     plan ends with MIPX_OP_JPEGE and the host only writes the header in front of the scan and EOI
     behind it (codec.jpeg_from_scan); a slot the engine could not fill runs again as `jpeg_coefs`.
     The bytes are the same either way.  Other outputs keep the RGB path.
+    jpeg_optimize: with jpeg_scan, the engine codes the scan with the image's own optimised Huffman
+    tables (libjpeg's optimize_coding, PARITY_ASSUMPTIONS.md row 24) and the file's DHT segments are
+    those: the same pixels in fewer bytes.  Without jpeg_scan it does nothing; a slot the engine could
+    not fill runs again as `jpeg_coefs`, with the Annex K tables, as it does today.
     jpeg_dct: hand a baseline 4:4:4 or 4:2:0 YCbCr JPEG to the engine as its quantisation tables and
     quantised coefficients (codec.decode_jpeg_coefs), so the host only entropy-decodes, when the
     request decodes at full size; the bytes are the same either way.  Shrink-on-load requests, the
@@ -685,33 +703,33 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         if take and jpeg_huff:
             px = _with_scan(buf, jpeg_huff_restart,
                             lambda slot: process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq,
-                                                 jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan))
+                                                 jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize))
         if px is None:
             dct = codec.decode_jpeg_coefs(buf) if take else None
             px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
-                         jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan)
+                         jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
     else:
         take = (jpeg_dct or jpeg_huff) and hdr.bands == 3 and itype == "jpeg"
         px = None
         if take and jpeg_huff:
             px = _with_scan(buf, jpeg_huff_restart,
                             lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts,
-                                                 wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq, jpeg_scan=jpeg_scan))
+                                                 wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize))
         dct = codec.decode_jpeg_coefs(buf) if take and px is None else None
         planes = codec.decode_ycc(buf) if px is None and dct is None and ycc and hdr.bands == 3 else None
         if px is not None:
             pass
         elif dct is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         jpeg_dct=dct, jpeg_quality=jq, jpeg_scan=jpeg_scan)
+                         jpeg_dct=dct, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
         elif planes is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         ycc=planes, jpeg_quality=jq, jpeg_scan=jpeg_scan)
+                         ycc=planes, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
         else:
             px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         jpeg_quality=jq, jpeg_scan=jpeg_scan)
+                         jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
     if isinstance(px, JpegScan):
-        body = codec.jpeg_from_scan(px.scan, px.w, px.h, px.layout, px.quality)
+        body = codec.jpeg_from_scan(px.scan, px.w, px.h, px.layout, px.quality, px.tables)
         return Image(body, codec.mime_type(codec.sniff_type(body)))
     if isinstance(px, JpegCoefs):
         body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)

@@ -161,7 +161,9 @@ enum {
                             ceil(w / shrink) x ceil(h / shrink) x 3: the pixels the JPEG of the image at that
                             quality decodes to at that scale (mipx_plan_add_jpeg_roundtrip)
                                   (MIPX_OP_JPEGC's rule, then MIPX_OP_JPEGD's with the same tables) */
-    MIPX_OP_JPEGE,       /* = 19, the entropy-coded scan: a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/
+    MIPX_OP_JPEGE,       /* = 19, the entropy-coded scan: a[0] = MIPX_YCC_*, a[1] = quality 1..100, a[2] = 0 for
+                            the Annex K Huffman tables or 1 for the image's own optimised ones (any other value
+                            is MIPX_EINVAL: this tightens a word that was ignored); out_w/out_h/
                             out_bands = the image it consumes (w, h, 3); only as the LAST step of a plan whose
                             image there has 3 bands, never together with MIPX_OP_JPEGC; the output buffer is
                             then one slot per image (mipx_plan_set_jpeg_scan_output)
@@ -241,8 +243,20 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * MIPX_JPEG_SCAN_UNCODABLE: a coefficient has no Annex K code (an AC magnitude above 1023 or a DC
  * difference above 2047 in magnitude, which MIPX_OP_JPEGC never makes of 8-bit pixels); length is 0;
  * it wins over OVERFLOW.  Nothing outside the slot is ever written; slots and both pointers start
- * on any byte. */
+ * on any byte.
+ *    With optimised tables (a[2] = 1, mipx_plan_set_jpeg_scan_output_optimized, the _optimized op
+ * calls; PARITY_ASSUMPTIONS.md row 24) the scan is coded with the four tables libjpeg's
+ * optimize_coding makes of the image's own symbol counts (jpeg_gen_optimal_table, tie-breaks
+ * included; Y counts into DC 0 / AC 0, Cb and Cr together into DC 1 / AC 1), and the slot carries
+ * them: mipx_jpeg_scan_opt_bytes(w, h, layout) = MIPX_JPEG_SCAN_OPT_HEADER_BYTES +
+ * mipx_jpegc_bytes(w, h, layout) bytes.  The first 16 bytes are (length, status, bits, 1); at byte 16
+ * stand four tables of 272 bytes, DC 0, DC 1, AC 0, AC 1, each the DHT's 16 counts and then the
+ * symbols, zero-padded: the layout of a MIPX_OP_JPEGH slot at byte 416, so one copies into the
+ * other; the scan starts at byte 1104.  The statuses mean what they mean above (a value without an
+ * Annex K code has no code here either); when the status is not OK the tables are unspecified.
+ * A scan of 64 x blocks >= 10^9 (libjpeg's search starts there) is MIPX_EINVAL for this variant. */
 #define MIPX_JPEG_SCAN_HEADER_BYTES 16
+#define MIPX_JPEG_SCAN_OPT_HEADER_BYTES 1104
 enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODABLE = 2 };
 #define MIPX_JPEGD_HEADER_BYTES 384
 /* Entropy-coded JPEG input (mipx_op_jpegh_*): the file's scan bytes instead of its coefficients, a
@@ -399,9 +413,14 @@ int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
  * chain stage only, after planar or coefficient input, a text watermark and a round trip in either
  * call order; and MIPX_EINVAL for a plan that already ends with MIPX_OP_JPEGC or MIPX_OP_JPEGE
  * (mipx_plan_set_jpegc_output and mipx_plan_add_jpeg_roundtrip likewise refuse a plan that ends
- * with MIPX_OP_JPEGE).  The request path copies whole slots to the host. */
+ * with MIPX_OP_JPEGE).  The request path copies whole slots to the host.
+ * mipx_jpeg_scan_opt_bytes and mipx_plan_set_jpeg_scan_output_optimized: the same for the step with
+ * optimised Huffman tables (a[2] = 1), whose slots are MIPX_JPEG_SCAN_OPT_HEADER_BYTES +
+ * mipx_jpegc_bytes(w, h, layout) bytes; also MIPX_EINVAL for an image of 10^9 / 64 scan blocks or more. */
 size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout);
 int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, int32_t quality);
+size_t mipx_jpeg_scan_opt_bytes(int32_t w, int32_t h, int32_t layout);
+int mipx_plan_set_jpeg_scan_output_optimized(mipx_plan *plan, int32_t layout, int32_t quality);
 /* JPEG coefficient input (MIPX_OP_JPEGD, see MIPX_JPEGD_HEADER_BYTES).  Both calls work without a GPU.
  * mipx_jpegd_bytes: bytes of one w x h image's payload, 384 + mipx_jpegc_bytes(w, h, layout); 0
  * for a non-positive size or an unknown layout.
@@ -534,6 +553,14 @@ int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int
                           int32_t layout, void *d_work, void *stream);
 int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                              int32_t layout, int32_t quality, void *d_work, void *stream);
+/* The same two with optimised Huffman tables: n slots of mipx_jpeg_scan_opt_bytes(w, h, layout) bytes,
+ * d_work of mipx_op_workspace_bytes(MIPX_OP_JPEGE, n, w, h, 3, 1.0, 0) bytes (8 KiB per image more: the
+ * symbol counts and the codes), two more launches in front (the histogram, the tables).  Also
+ * MIPX_EINVAL for an image of 10^9 / 64 scan blocks or more. */
+int mipx_op_jpegc_to_scan_optimized(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                    int32_t layout, void *d_work, void *stream);
+int mipx_op_rgb_to_jpeg_scan_optimized(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                       int32_t layout, int32_t quality, void *d_work, void *stream);
 /* The entropy decoder (see MIPX_JPEGH_HEADER_BYTES): n slots (n * mipx_jpegh_bytes(w, h, layout)
  * bytes) -> n payloads of MIPX_OP_JPEGD (n * mipx_jpegd_bytes(w, h, layout) bytes) and n uint32
  * statuses (MIPX_JPEGH_*).  mipx_jpegh_bytes works without a GPU: MIPX_JPEGH_HEADER_BYTES +

@@ -11,6 +11,7 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpegrt420 --w 3840 --h 2160 --n 64 --q 75
     python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75     (RGB -> entropy-coded scan)
     python scripts/op_bench.py jpegcs420 --w 3840 --h 2160 --n 64 --q 75    (the entropy coder alone)
+    python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75 --optimize   (with optimised Huffman tables)
     python scripts/op_bench.py jpegh420 --w 3840 --h 2160 --n 64 --q 75     (entropy-coded scan -> RGB)
     python scripts/op_bench.py jpeghd420 --w 3840 --h 2160 --n 64 --q 75    (the entropy decoder alone)
     python scripts/op_bench.py jpegh420 --file tests/golden/testdata/large.jpg --n 64   (a photograph's scan)
@@ -64,6 +65,8 @@ def main():
                     help="jpegh* / jpeghd*: n copies of one file that Pillow writes at --q of the pixels (of --file, else "
                          "noise) with a restart interval of N MCUs, or of R MCU rows as rR; 0: the same file without "
                          "restart markers, the twin to compare with")
+    ap.add_argument("--optimize", action="store_true",
+                    help="jpege* / jpegcs*: optimised Huffman tables (the *_optimized calls; the slots carry the tables)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -133,7 +136,7 @@ def main():
         b = ob = 3
         layout = 1 if a.op.endswith("420") else 0
         in_img = w * h * 3 if a.op.startswith("jpege") else lib.mipx_jpegc_bytes(w, h, layout)
-        out_img = lib.mipx_jpeg_scan_bytes(w, h, layout)
+        out_img = (lib.mipx_jpeg_scan_opt_bytes if a.optimize else lib.mipx_jpeg_scan_bytes)(w, h, layout)
     JPEGH = ("jpegh420", "jpegh444", "jpeghd420", "jpeghd444")
     file_slot = None
     if a.op in JPEGH:   # one input slot per image in; RGB (jpegh*) or MIPX_OP_JPEGD's payload (jpeghd*) out
@@ -173,7 +176,8 @@ def main():
     y = torch.empty((n * out_img,), dtype=torch.uint8, device=dev)
     ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
     if a.op in JPEGE:
-        ws = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
+        ws = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 1.0 if a.optimize else 0.0, 0.0),), dtype=torch.uint8,
+                         device=dev)
     if a.op in JPEGH:
         import numpy as np
         ws = torch.empty((lib.mipx_op_workspace_bytes(20, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
@@ -273,8 +277,12 @@ def main():
         if a.op in ("jpegrt420", "jpegrt444"):
             return lib.mipx_op_jpeg_roundtrip(X, Y, n, w, h, layout, a.q, a.shrink, WS, WSB, sp)
         if a.op in ("jpege420", "jpege444"):
+            if a.optimize:
+                return lib.mipx_op_rgb_to_jpeg_scan_optimized(X, Y, n, w, h, layout, a.q, WS, sp)
             return lib.mipx_op_rgb_to_jpeg_scan(X, Y, n, w, h, layout, a.q, WS, sp)
         if a.op in ("jpegcs420", "jpegcs444"):
+            if a.optimize:
+                return lib.mipx_op_jpegc_to_scan_optimized(X, Y, n, w, h, layout, WS, sp)
             return lib.mipx_op_jpegc_to_scan(X, Y, n, w, h, layout, WS, sp)
         if a.op in ("jpegh420", "jpegh444"):
             return lib.mipx_op_jpegh_to_rgb(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
@@ -316,7 +324,7 @@ def main():
         ms = measure()
         if a.op in JPEGE:   # what the slots say: the scans' mean length against the slot's capacity
             head = y.view(n, out_img)[:, :16].cpu().numpy().view("<u4")
-            line.update(q=a.q, capacity=out_img - 16, mean_length=round(float(head[:, 0].mean()), 1),
+            line.update(q=a.q, optimize=a.optimize, capacity=out_img - (1104 if a.optimize else 16), mean_length=round(float(head[:, 0].mean()), 1),
                         statuses=sorted(set(head[:, 1].tolist())))
         if a.op in JPEGH:   # the statuses, and what a request uploads next to its RGB
             lengths = x.view(n, in_img)[:, :4].cpu().numpy().view("<u4")
