@@ -15,6 +15,7 @@ from .engine import (DeviceBuffer, Engine, GuardedBuffer, device_count, execute,
                      plan_set_jpegd_input, plan_set_jpegd_input_scaled, jpegd_bytes, jpegd_to_rgb,
                      jpegd_to_rgb_scaled, plan_add_jpeg_roundtrip, jpeg_roundtrip,
                      plan_set_jpeg_scan_output, jpeg_scan_bytes, jpeg_scan_opt_bytes, rgb_to_jpeg_scan, jpegc_to_scan, scan_slot,
+                     rgb_to_jpeg_scan_packed, jpegc_to_scan_packed, scan_unpack,
                      jpegh_bytes, plan_set_jpegh_input, plan_set_jpegh_input_scaled, execute_status, jpegh_to_jpegd, jpegh_to_rgb, jpegh_to_rgb_scaled, JPEGH_OK, JPEGH_UNSYNCED,
                      JPEGH_BAD)
 

@@ -176,6 +176,11 @@ _SIG = {
     "mipx_op_rgb_to_jpeg_scan": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P]),
     "mipx_op_jpegc_to_scan_optimized": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, _P]),
     "mipx_op_rgb_to_jpeg_scan_optimized": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P]),
+    "mipx_op_jpegc_to_scan_packed": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "mipx_op_rgb_to_jpeg_scan_packed": (C.c_int, [_U8P, _U8P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "mipx_jpeg_scan_packed_dir_bytes": (C.c_size_t, [_I]),
+    "mipx_jpeg_scan_unpack": (C.c_int, [_P, _I, _U8P, C.c_size_t, _I, C.c_size_t, _U8P, C.c_size_t]),
+    "mipx_transfer_stats": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mipx_jpegh_bytes": (C.c_size_t, [_I, _I, _I]),
     "mipx_plan_set_jpegh_input": (C.c_int, [C.POINTER(MipxPlan), _I]),
     "mipx_plan_set_jpegh_input_scaled": (C.c_int, [C.POINTER(MipxPlan), _I, _I, _I, _I]),

@@ -22,6 +22,17 @@
 //                    capacity; the header
 // Images whose verdict is not "ok" are skipped by every later kernel but for the header.
 //
+// Packed output (mipx_op_*_scan_packed, the request path's download): the slots stand back to back,
+// each rounded up to 16 bytes, instead of a capacity apart.  Every image's final length is known
+// after k_jpege_scan<1>, before a byte of output is stored, so one launch goes in between and no
+// byte moves twice:
+//   k_jpege_place    one workgroup over the n images: the directory, n + 1 byte offsets, off[i + 1] =
+//                    off[i] + align16(head + length), a slot that is not "ok" being its header alone
+// and k_jpege_stuff<true> takes a slot's base from the directory and stores nothing but the header
+// and `length` bytes.  With optimised tables k_jpege_tables<true> parks the four DHTs in the image's
+// histogram, which it has read by then, and k_jpege_stuff<true> copies them behind the header: no
+// launch more than that one.
+//
 // With optimised tables (PARITY_ASSUMPTIONS.md row 24) two launches go in front, and the count and
 // pack kernels read the image's own codes from the workspace instead of the Annex K ones:
 //   k_jpege_hist     the same lanes walk their blocks once and count the symbols: a histogram of
@@ -79,6 +90,8 @@ struct JpegeArgs {
     uint32_t mw;              // MCUs across
     uint32_t cb_off, cr_off;  // byte offsets of the Cb and Cr coefficients
     uint32_t blocks, tiles, chunks;  // per image: blocks of the scan, tiles of them, chunks of the stream
+    unsigned long long *dir;  // packed output only: n + 1 byte offsets of the slots in `out`
+    uint32_t n;               // images
 };
 
 __constant__ uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -342,6 +355,9 @@ __device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, i
 // then largest index); every entry of either tree then grows by one bit and joins c1's, which is
 // what the library's walk along its `others` chains does.  The waves run different numbers of merges
 // and meet again at the barriers behind them.
+// PACKED: the slot's place is not known yet, so the DHTs go to the head of the image's histogram
+// (every wave has its counts in registers before the first barrier) for k_jpege_stuff to copy.
+template <bool PACKED>
 __global__ void __launch_bounds__(kTile) k_jpege_tables(const JpegeArgs a) {
     __shared__ uint32_t size_of[4][256];          // raw code size per symbol, 0: not in the table
     __shared__ uint32_t bits[4][kMaxLen + 1];     // codes per length, raw and then limited
@@ -432,7 +448,9 @@ __global__ void __launch_bounds__(kTile) k_jpege_tables(const JpegeArgs a) {
     }
     __syncthreads();
     // the slot's tables are DC 0, DC 1, AC 0, AC 1
-    u8 *to = a.out + static_cast<size_t>(img) * (static_cast<size_t>(a.head) + a.cap) + MIPX_JPEG_SCAN_HEADER_BYTES +
+    u8 *to = (PACKED ? reinterpret_cast<u8 *>(a.hist + static_cast<size_t>(img) * (4u * kJpegeCodesPerTable))
+                     : a.out + static_cast<size_t>(img) * (static_cast<size_t>(a.head) + a.cap) +
+                           MIPX_JPEG_SCAN_HEADER_BYTES) +
              ((t & 1u) * 2u + (t >> 1)) * kJpegDhtBytes;
     for (uint32_t i = lane; i < kJpegDhtBytes; i += 64u) to[i] = dht[t][i];
 }
@@ -540,17 +558,54 @@ __global__ void __launch_bounds__(kTile) k_jpege_ffcount(const JpegeArgs a) {
     if (threadIdx.x == 0) a.chunk_sums[static_cast<size_t>(img) * a.chunks + chunk] = total;
 }
 
+// What the slot's header says of its scan: the bytes behind the header when the status is "ok", a
+// lower bound of the need when it is "overflow".
+__device__ __forceinline__ unsigned long long slot_length(const JpegeInfo *info) {
+    const unsigned long long bytes = (info->bits + 7ull) >> 3;
+    return info->status == MIPX_JPEG_SCAN_OK ? bytes + info->ff : info->status == MIPX_JPEG_SCAN_OVERFLOW ? bytes : 0ull;
+}
+
+// One workgroup: the packed slots' directory.  A slot takes its header and, when "ok", its scan
+// (which fits the capacity, so off[n] <= n slots' bytes), rounded up to 16 bytes.  The sums run in
+// units of 16 bytes, split in two 16-bit halves: 256 slots of nearly 2^32 bytes pass 32 bits.
+__global__ void __launch_bounds__(kTile) k_jpege_place(const JpegeArgs a) {
+    __shared__ uint32_t wsum[kTile / 64];
+    const uint32_t tid = threadIdx.x;
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < a.n; base += kTile) {
+        const uint32_t i = base + tid;
+        unsigned long long units = 0;
+        if (i < a.n) {
+            const JpegeInfo *info = a.info + i;
+            units = (a.head + (info->status == MIPX_JPEG_SCAN_OK ? slot_length(info) : 0ull) + 15ull) >> 4;
+        }
+        uint32_t lo_total, hi_total;
+        const uint32_t lo = block_scan(static_cast<uint32_t>(units & 0xffffu), wsum, &lo_total);
+        const uint32_t hi = block_scan(static_cast<uint32_t>(units >> 16), wsum, &hi_total);
+        if (i < a.n) a.dir[i + 1] = (carry + (static_cast<unsigned long long>(hi) << 16) + lo + units) << 4;
+        carry += (static_cast<unsigned long long>(hi_total) << 16) + lo_total;
+    }
+    if (tid == 0) a.dir[0] = 0ull;
+}
+
+// PACKED: the slot starts where the directory says, and nothing is stored but its header (with the
+// tables k_jpege_tables<true> parked) and its `length` bytes: not the pad up to the next slot.
+template <bool PACKED>
 __global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
     __shared__ uint32_t wsum[kTile / 64];
     const uint32_t img = blockIdx.y, chunk = blockIdx.x;
     const JpegeInfo *info = a.info + img;
-    u8 *slot = a.out + static_cast<size_t>(img) * (static_cast<size_t>(a.head) + a.cap);
+    u8 *slot = a.out + (PACKED ? static_cast<size_t>(a.dir[img])
+                               : static_cast<size_t>(img) * (static_cast<size_t>(a.head) + a.cap));
     const uint32_t status = info->status;
     const unsigned long long bits = info->bits, bytes = (bits + 7ull) >> 3;
+    if (PACKED && chunk == 0 && a.head != MIPX_JPEG_SCAN_HEADER_BYTES) {  // the four tables, a dword per lane
+        const u8 *dht = reinterpret_cast<const u8 *>(a.hist + static_cast<size_t>(img) * (4u * kJpegeCodesPerTable));
+        for (uint32_t i = threadIdx.x * 4u; i < 4u * kJpegDhtBytes; i += kTile * 4u)
+            __builtin_memcpy(slot + MIPX_JPEG_SCAN_HEADER_BYTES + i, dht + i, 4);  // any alignment
+    }
     if (chunk == 0 && threadIdx.x == 0) {
-        const unsigned long long length = status == MIPX_JPEG_SCAN_OK         ? bytes + info->ff
-                                          : status == MIPX_JPEG_SCAN_OVERFLOW ? bytes
-                                                                              : 0ull;
+        const unsigned long long length = slot_length(info);
         uint4 hdr;
         hdr.x = length > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(length);
         hdr.y = status;
@@ -581,11 +636,12 @@ __global__ void __launch_bounds__(kTile) k_jpege_stuff(const JpegeArgs a) {
 }  // namespace
 
 int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, bool optimise, u8 *work,
-                 hipStream_t st) {
+                 hipStream_t st, unsigned long long *d_dir) {
     const JpegeWork W(n, w, h, optimise);
     const bool sub = layout == MIPX_YCC_420;
     JpegeArgs a;
     a.coefs = d_coefs, a.out = d_out;
+    a.dir = d_dir, a.n = static_cast<uint32_t>(n);
     a.hist = reinterpret_cast<uint32_t *>(work + W.hist);
     a.opt_codes = reinterpret_cast<uint32_t *>(work + W.opt_codes);
     a.codes = optimise ? a.opt_codes : device_jpege_codes();
@@ -622,7 +678,8 @@ int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, 
         if (sub) hipLaunchKernelGGL(k_jpege_hist<MIPX_YCC_420>, by_tile, threads, 0, st, a);
         else hipLaunchKernelGGL(k_jpege_hist<MIPX_YCC_444>, by_tile, threads, 0, st, a);
         if ((e = launch_check("k_jpege_hist"))) return e;
-        hipLaunchKernelGGL(k_jpege_tables, by_image, threads, 0, st, a);
+        if (d_dir) hipLaunchKernelGGL(k_jpege_tables<true>, by_image, threads, 0, st, a);
+        else hipLaunchKernelGGL(k_jpege_tables<false>, by_image, threads, 0, st, a);
         if ((e = launch_check("k_jpege_tables"))) return e;
     }
     if (sub) hipLaunchKernelGGL(k_jpege_count<MIPX_YCC_420>, by_tile, threads, 0, st, a);
@@ -637,8 +694,14 @@ int jpege_launch(const u8 *d_coefs, u8 *d_out, int n, int w, int h, int layout, 
     if ((e = launch_check("k_jpege_ffcount"))) return e;
     hipLaunchKernelGGL(k_jpege_scan<1>, by_image, threads, 0, st, a);
     if ((e = launch_check("k_jpege_scan<1>"))) return e;
-    hipLaunchKernelGGL(k_jpege_stuff, by_chunk, threads, 0, st, a);
-    return launch_check("k_jpege_stuff");
+    if (!d_dir) {
+        hipLaunchKernelGGL(k_jpege_stuff<false>, by_chunk, threads, 0, st, a);
+        return launch_check("k_jpege_stuff");
+    }
+    hipLaunchKernelGGL(k_jpege_place, dim3(1), threads, 0, st, a);
+    if ((e = launch_check("k_jpege_place"))) return e;
+    hipLaunchKernelGGL(k_jpege_stuff<true>, by_chunk, threads, 0, st, a);
+    return launch_check("k_jpege_stuff<packed>");
 }
 
 }  // namespace mipx

@@ -215,9 +215,11 @@ int jpegrt_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int l
 // k_jpege.hip: the coefficients k_jpegc writes -> one output slot per image (mipx_jpeg_scan_bytes): the
 // Huffman-coded, padded and stuffed scan behind a 16-byte header; with `optimise` coded with the image's own
 // tables (row 24), which stand behind the header (mipx_jpeg_scan_opt_bytes).  work: a JpegeWork of
-// (n, w, h, optimise), 16-byte aligned
+// (n, w, h, optimise), 16-byte aligned.  With d_dir (device memory, 8-byte aligned, n + 1 offsets) the slots
+// are packed back to back instead, each rounded up to 16 bytes: d_dir[i] is slot i's byte offset in `out`,
+// d_dir[n] the end; only a slot's header and its `length` bytes are written
 int jpege_launch(const uint8_t *coefs, uint8_t *out, int n, int w, int h, int layout, bool optimise, uint8_t *work,
-                 hipStream_t st);
+                 hipStream_t st, unsigned long long *d_dir = nullptr);
 // The coder's workspace, sized without the layout (both fit): byte offsets of its parts, each a multiple
 // of 256, and the total.  Per image: cap = 384 ceil(w / 8) ceil(h / 8) bytes, the 4:4:4 coefficients;
 // blocks = the scan's blocks, dummy ones included, of whichever layout has more.

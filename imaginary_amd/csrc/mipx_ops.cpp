@@ -190,15 +190,18 @@ static int jpege_check(const char *what, const void *d_in, const void *d_out, co
     return MIPX_OK;
 }
 
+// d_dir: nullptr for whole slots, else the packed slots' directory (device memory, 8-byte aligned)
 static int jpegc_to_scan(const char *what, const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
-                         int32_t layout, bool optimise, void *d_work, void *stream) {
+                         int32_t layout, bool optimise, void *d_work, void *stream, uint64_t *d_dir = nullptr) {
     const int e = jpege_check(what, d_coefs, d_out, d_work, n, w, h, layout, optimise);
     if (e) return e;
-    return jpege_launch(d_coefs, d_out, n, w, h, layout, optimise, static_cast<uint8_t *>(d_work), as_stream(stream));
+    return jpege_launch(d_coefs, d_out, n, w, h, layout, optimise, static_cast<uint8_t *>(d_work), as_stream(stream),
+                        reinterpret_cast<unsigned long long *>(d_dir));
 }
 
 static int rgb_to_jpeg_scan(const char *what, const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
-                            int32_t layout, int32_t quality, bool optimise, void *d_work, void *stream) {
+                            int32_t layout, int32_t quality, bool optimise, void *d_work, void *stream,
+                            uint64_t *d_dir = nullptr) {
     if (quality < 1 || quality > 100) return MIPX_EINVAL;
     int e = jpege_check(what, d_in, d_out, d_work, n, w, h, layout, optimise);
     if (e) return e;
@@ -206,7 +209,18 @@ static int rgb_to_jpeg_scan(const char *what, const uint8_t *d_in, uint8_t *d_ou
     uint8_t *coefs = work + JpegeWork(n, w, h, optimise).coefs;  // packed as mipx_jpegc_bytes per image
     e = jpegc_launch(d_in, coefs, n, w, h, layout, quality, as_stream(stream));
     if (e) return e;
-    return jpege_launch(coefs, d_out, n, w, h, layout, optimise, work, as_stream(stream));
+    return jpege_launch(coefs, d_out, n, w, h, layout, optimise, work, as_stream(stream),
+                        reinterpret_cast<unsigned long long *>(d_dir));
+}
+
+// What the two packed calls check of their own arguments.
+static int packed_check(const char *what, int32_t optimize, const uint64_t *d_dir) {
+    if (!d_dir || (optimize != 0 && optimize != 1)) return MIPX_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_dir) & 7u) {
+        set_error("%s: the directory is not 8-byte aligned", what);
+        return MIPX_EINVAL;
+    }
+    return MIPX_OK;
 }
 
 int mipx_op_jpegc_to_scan(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
@@ -227,6 +241,23 @@ int mipx_op_rgb_to_jpeg_scan(const uint8_t *d_in, uint8_t *d_out, int32_t n, int
 int mipx_op_rgb_to_jpeg_scan_optimized(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                                        int32_t layout, int32_t quality, void *d_work, void *stream) {
     return rgb_to_jpeg_scan("rgb to optimised jpeg scan", d_in, d_out, n, w, h, layout, quality, true, d_work, stream);
+}
+
+int mipx_op_jpegc_to_scan_packed(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                 int32_t layout, void *d_work, void *stream, int32_t optimize, uint64_t *d_dir) {
+    const char *what = "jpeg coefficients to packed scans";
+    const int e = packed_check(what, optimize, d_dir);
+    if (e) return e;
+    return jpegc_to_scan(what, d_coefs, d_out, n, w, h, layout, optimize == 1, d_work, stream, d_dir);
+}
+
+int mipx_op_rgb_to_jpeg_scan_packed(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                    int32_t layout, int32_t quality, void *d_work, void *stream, int32_t optimize,
+                                    uint64_t *d_dir) {
+    const char *what = "rgb to packed jpeg scans";
+    const int e = packed_check(what, optimize, d_dir);
+    if (e) return e;
+    return rgb_to_jpeg_scan(what, d_in, d_out, n, w, h, layout, quality, optimize == 1, d_work, stream, d_dir);
 }
 
 // The checks the three entropy-decoder calls share; *work: the workspace.

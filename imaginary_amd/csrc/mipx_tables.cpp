@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "mipx.h"
 #include "mipx_tables.h"
 
 namespace mipx {
@@ -492,3 +493,38 @@ int jpeg_optimal_table(const uint32_t freq[256], uint8_t dht[kJpegDhtBytes], uin
 }
 
 }  // namespace mipx
+
+// ---- packed scan slots (k_jpege.hip's packed mode): the host side, HIP-free --------------------
+namespace mipx {
+
+bool scan_dir_ok(const uint64_t *dir, int32_t n, size_t head, size_t packed_bytes) {
+    if (!dir || n <= 0 || head < MIPX_JPEG_SCAN_HEADER_BYTES || dir[0] != 0) return false;
+    for (int32_t i = 0; i < n; ++i) {
+        if (dir[i + 1] < dir[i]) return false;
+        const uint64_t step = dir[i + 1] - dir[i];
+        if ((step & 15u) || step < head) return false;
+    }
+    return dir[n] <= packed_bytes;
+}
+
+}  // namespace mipx
+
+extern "C" size_t mipx_jpeg_scan_packed_dir_bytes(int32_t n) {
+    return n > 0 ? 8 * (static_cast<size_t>(n) + 1) : 0;
+}
+
+extern "C" int mipx_jpeg_scan_unpack(const uint64_t *dir, int32_t n, const uint8_t *packed, size_t packed_bytes, int32_t i,
+                                     size_t head, uint8_t *slot, size_t slot_bytes) {
+    if (!dir || !packed || !slot || n <= 0 || i < 0 || i >= n) return MIPX_EINVAL;
+    if (head != MIPX_JPEG_SCAN_HEADER_BYTES && head != MIPX_JPEG_SCAN_OPT_HEADER_BYTES) return MIPX_EINVAL;
+    if (!mipx::scan_dir_ok(dir, n, head, packed_bytes)) return MIPX_EDATA;
+    const uint8_t *from = packed + dir[i];
+    uint32_t length, status;
+    std::memcpy(&length, from, 4);
+    std::memcpy(&status, from + 4, 4);
+    // an OVERFLOW header's length is a need, above the capacity: it has no bytes behind it
+    const uint64_t bytes = head + (status == MIPX_JPEG_SCAN_OK ? static_cast<uint64_t>(length) : 0u);
+    if (bytes > dir[i + 1] - dir[i] || bytes > slot_bytes) return MIPX_EDATA;
+    std::memcpy(slot, from, static_cast<size_t>(bytes));
+    return MIPX_OK;
+}

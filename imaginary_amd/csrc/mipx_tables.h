@@ -83,4 +83,9 @@ HostTable build_jpege_codes();
 constexpr int kJpegDhtBytes = 272;
 int jpeg_optimal_table(const uint32_t freq[256], uint8_t dht[kJpegDhtBytes], uint32_t codes[kJpegeCodesPerTable]);
 
+// The directory of packed scan slots (mipx_op_*_scan_packed) as mipx_jpeg_scan_unpack and the request
+// path's completer take it: off[0] = 0, non-decreasing, every step a multiple of 16 and at least
+// `head`, off[n] <= packed_bytes.
+bool scan_dir_ok(const uint64_t *dir, int32_t n, size_t head, size_t packed_bytes);
+
 }  // namespace mipx

@@ -21,6 +21,7 @@ __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
            "plan_set_jpeg_scan_output", "jpeg_scan_bytes", "jpeg_scan_opt_bytes", "rgb_to_jpeg_scan", "jpegc_to_scan", "scan_slot",
+           "rgb_to_jpeg_scan_packed", "jpegc_to_scan_packed", "scan_unpack",
            "jpegh_bytes", "plan_set_jpegh_input", "plan_set_jpegh_input_scaled", "execute_status", "jpegh_to_jpegd", "jpegh_to_rgb", "jpegh_to_rgb_scaled", "JPEGH_OK", "JPEGH_UNSYNCED", "JPEGH_BAD",
            "fit_dimension", "Engine",
            "run_op", "execute", "device_count", "synchronize", "set_reduce_sampling", "reduce_sampling"]
@@ -551,6 +552,12 @@ class Engine:
         check(lib.mipx_stats(device, C.byref(b), C.byref(r)), "mipx_stats")
         return b.value, r.value
 
+    def transfer_stats(self, queue: int = 0):
+        """(H2D bytes, D2H bytes) the request path has enqueued on `queue` since mipx_init."""
+        a, b = C.c_uint64(), C.c_uint64()
+        check(lib.mipx_transfer_stats(queue, C.byref(a), C.byref(b)), "mipx_transfer_stats")
+        return a.value, b.value
+
     def queue_stats(self):
         """[(device, batches, requests, pending_bytes)] for every request queue."""
         out = []
@@ -751,6 +758,69 @@ def jpegc_to_scan(coefs: np.ndarray, w: int, h: int, layout: int, optimize: bool
     synchronize()
     _check_guards(what, din, dout, ws)
     return dout.download((n, need))
+
+
+def _packed_result(what: str, n: int, need: int, call, w: int, din, ws):
+    """The output side the two packed calls share: the slots' buffer, the workspace and the directory
+    (behind 8 spare bytes, so that the output skew keeps it 8-byte aligned), the call, (dir, packed)."""
+    dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
+    ddir = _dev("out", what, 8 * (n + 1) + 8)
+    at = ddir.ptr + (-ddir.ptr) % 8
+    check(call(dout, at), what)
+    synchronize()
+    _check_guards(what, din, dout, ddir, ws)
+    d = np.empty(n + 1, "<u8")
+    check(lib.mipx_memcpy_d2h(d.ctypes.data, at, d.nbytes), "mipx_memcpy_d2h")
+    return d, dout.download((n * need,))
+
+
+def rgb_to_jpeg_scan_packed(imgs: np.ndarray, layout: int, quality: int, optimize: bool = False):
+    """mipx_op_rgb_to_jpeg_scan_packed on (h, w, 3) or (n, h, w, 3) uint8; returns (dir, packed): the n + 1
+    uint64 offsets and the whole output buffer, n * jpeg_scan_bytes (jpeg_scan_opt_bytes with `optimize`)
+    uint8, of which only each slot's header and scan were written (scan_unpack takes one slot out)."""
+    sync_tuning()
+    x = _batch(imgs)
+    n, h, w, b = x.shape
+    need = (jpeg_scan_opt_bytes if optimize else jpeg_scan_bytes)(w, h, layout)
+    if b != 3 or need == 0:
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
+    what = "mipx_op_rgb_to_jpeg_scan_packed"
+    din = _dev("in", what, x.nbytes, w * 3, x)
+    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 1.0 if optimize else 0.0, 0.0))
+    out = _packed_result(what, n, need, lambda dout, ddir: lib.mipx_op_rgb_to_jpeg_scan_packed(
+        din.ptr, dout.ptr, n, w, h, layout, quality, ws.ptr, None, int(bool(optimize)), ddir), w, din, ws)
+    return out
+
+
+def jpegc_to_scan_packed(coefs: np.ndarray, w: int, h: int, layout: int, optimize: bool = False):
+    """mipx_op_jpegc_to_scan_packed on coefficients as rgb_to_jpegc returns them; returns (dir, packed) as
+    rgb_to_jpeg_scan_packed does."""
+    sync_tuning()
+    x = np.ascontiguousarray(coefs, dtype=np.int16)
+    if x.ndim == 1:
+        x = x[None]
+    have = jpegc_bytes(w, h, layout)
+    if x.ndim != 2 or have == 0 or x.shape[1] * 2 != have:
+        raise ValueError(f"coefficients of shape {np.shape(coefs)} for {w}x{h} layout {layout}: {have // 2} per image")
+    n, need = x.shape[0], (jpeg_scan_opt_bytes if optimize else jpeg_scan_bytes)(w, h, layout)
+    what = "mipx_op_jpegc_to_scan_packed"
+    din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x.view(np.uint8))
+    ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 1.0 if optimize else 0.0, 0.0))
+    out = _packed_result(what, n, need, lambda dout, ddir: lib.mipx_op_jpegc_to_scan_packed(
+        din.ptr, dout.ptr, n, w, h, layout, ws.ptr, None, int(bool(optimize)), ddir), w, din, ws)
+    return out
+
+
+def scan_unpack(dir, packed, i: int, head: int, slot_bytes: int) -> np.ndarray:
+    """mipx_jpeg_scan_unpack: slot i of packed slots as a buffer of slot_bytes uint8 that starts out 0xA5
+    and holds the slot's header (`head` bytes: 16, or 1104 with optimised tables) and its scan; MipxError
+    (MIPX_EDATA) for a directory or a header that is inconsistent.  Runs on the host, without a GPU."""
+    d = np.ascontiguousarray(dir, dtype="<u8")
+    p = np.ascontiguousarray(packed, dtype=np.uint8).ravel()
+    slot = np.full(int(slot_bytes), 0xA5, np.uint8)
+    check(lib.mipx_jpeg_scan_unpack(d.ctypes.data, d.size - 1, p.ctypes.data, p.size, i, head, slot.ctypes.data,
+                                    slot.size), "mipx_jpeg_scan_unpack")
+    return slot
 
 
 def jpegd_to_rgb(payload: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:

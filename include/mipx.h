@@ -41,7 +41,8 @@
  *    A plan that ends with MIPX_OP_JPEGC, and mipx_op_rgb_to_jpegc, write n * mipx_jpegc_bytes()
  *    output bytes instead (JPEG coefficients), at any alignment.
  *    A plan that ends with MIPX_OP_JPEGE, mipx_op_rgb_to_jpeg_scan and mipx_op_jpegc_to_scan write
- *    n * mipx_jpeg_scan_bytes() output bytes instead (entropy-coded scans), at any alignment.
+ *    n * mipx_jpeg_scan_bytes() output bytes instead (entropy-coded scans), at any alignment; the _packed
+ *    calls write, inside the same n slots' bytes, only each slot's header and scan at its directory offset.
  *    A plan that starts with MIPX_OP_JPEGD, and mipx_op_jpegd_to_rgb, read n * mipx_jpegd_bytes()
  *    input bytes instead (quantisation tables + JPEG coefficients), at any alignment.
  *    A plan that starts with MIPX_OP_JPEGH, and mipx_op_jpegh_to_*, read n slots of
@@ -254,7 +255,12 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * symbols, zero-padded: the layout of a MIPX_OP_JPEGH slot at byte 416, so one copies into the
  * other; the scan starts at byte 1104.  The statuses mean what they mean above (a value without an
  * Annex K code has no code here either); when the status is not OK the tables are unspecified.
- * A scan of 64 x blocks >= 10^9 (libjpeg's search starts there) is MIPX_EINVAL for this variant. */
+ * A scan of 64 x blocks >= 10^9 (libjpeg's search starts there) is MIPX_EINVAL for this variant.
+ *    Packed slots (mipx_op_rgb_to_jpeg_scan_packed, mipx_op_jpegc_to_scan_packed; what the request path
+ * downloads): the same slots back to back in the same output buffer, each rounded up to 16 bytes, behind a
+ * directory of n + 1 uint64 byte offsets; a slot is then its header (and tables) and its `length` bytes, a
+ * slot that is not OK its header alone, and no other byte of the buffer is written.  mipx_jpeg_scan_unpack
+ * takes one slot out of a downloaded buffer on the host. */
 #define MIPX_JPEG_SCAN_HEADER_BYTES 16
 #define MIPX_JPEG_SCAN_OPT_HEADER_BYTES 1104
 enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODABLE = 2 };
@@ -413,7 +419,8 @@ int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[64]);
  * chain stage only, after planar or coefficient input, a text watermark and a round trip in either
  * call order; and MIPX_EINVAL for a plan that already ends with MIPX_OP_JPEGC or MIPX_OP_JPEGE
  * (mipx_plan_set_jpegc_output and mipx_plan_add_jpeg_roundtrip likewise refuse a plan that ends
- * with MIPX_OP_JPEGE).  The request path copies whole slots to the host.
+ * with MIPX_OP_JPEGE).  The request path downloads each slot's header (and tables) and `length` bytes only,
+ * and writes only those into the caller's buffer (MIPX_SCAN_TRIM=0 at mipx_init: whole slots).
  * mipx_jpeg_scan_opt_bytes and mipx_plan_set_jpeg_scan_output_optimized: the same for the step with
  * optimised Huffman tables (a[2] = 1), whose slots are MIPX_JPEG_SCAN_OPT_HEADER_BYTES +
  * mipx_jpegc_bytes(w, h, layout) bytes; also MIPX_EINVAL for an image of 10^9 / 64 scan blocks or more. */
@@ -485,6 +492,11 @@ int mipx_pick_queue(int32_t device, const int32_t *queue_device, const int64_t *
                     int32_t n_queues);
 int mipx_queue_stats(int queue, int32_t *device, uint64_t *batches, uint64_t *requests,
                      int64_t *pending_bytes);         /* pending = queued input bytes */
+/* What crosses the host link: the bytes the request path has enqueued in each direction on `queue`
+ * since mipx_init, every copy counted (inputs, watermarks, outputs, MIPX_OP_JPEGH statuses, packed-scan
+ * directories).  Either pointer may be NULL.  MIPX_ENOTINIT before mipx_init, MIPX_EINVAL for a queue
+ * that does not exist. */
+int mipx_transfer_stats(int queue, uint64_t *h2d_bytes, uint64_t *d2h_bytes);
 
 /* ---- device-resident batch API ---- */
 size_t mipx_workspace_bytes(const mipx_plan *plan, int32_t n);
@@ -561,6 +573,30 @@ int mipx_op_jpegc_to_scan_optimized(const uint8_t *d_coefs, uint8_t *d_out, int3
                                     int32_t layout, void *d_work, void *stream);
 int mipx_op_rgb_to_jpeg_scan_optimized(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                                        int32_t layout, int32_t quality, void *d_work, void *stream);
+/* The same coder with its slots packed back to back, so that a caller downloads the scans and not the
+ * capacity: the arguments of the unpacked calls, then optimize (0: Annex K tables, 1: optimised; any other
+ * value is MIPX_EINVAL) and d_dir, device memory for n + 1 little-endian uint64 byte offsets
+ * (mipx_jpeg_scan_packed_dir_bytes(n) = 8 (n + 1) bytes; 8-byte aligned, else MIPX_EINVAL).  d_out and
+ * d_work have the sizes of the unpacked calls.  With head = 16, or 1104 with optimised tables:
+ *   off[0] = 0,  off[i + 1] = off[i] + align16(head + (status_i == MIPX_JPEG_SCAN_OK ? length_i : 0))
+ * Slot i stands at d_out + off[i] and is what the unpacked call writes, up to its `length`: the header
+ * (the tables) and the scan.  A slot that is OVERFLOW or UNCODABLE is its header alone (an OVERFLOW
+ * header's length is above the capacity and means no bytes).  Only [off[i], off[i] + head + length_i) is
+ * written: not the pad bytes up to off[i + 1], nothing at or past off[n]; off[n] <= n slots' bytes.  One
+ * launch of one workgroup more than the unpacked call; nothing is moved twice.
+ * mipx_jpeg_scan_unpack, on the host and without a GPU: checks a downloaded directory (off[0] = 0,
+ * non-decreasing, every step a multiple of 16 and >= head, off[n] <= packed_bytes), reads slot i's header
+ * and copies head + (status == OK ? length : 0) bytes to `slot`, after checking that amount against
+ * off[i + 1] - off[i] and slot_bytes.  MIPX_EINVAL for NULL pointers, n <= 0, i outside 0..n-1 or a head
+ * that is neither size; MIPX_EDATA, with nothing written, for anything inconsistent. */
+int mipx_op_jpegc_to_scan_packed(const uint8_t *d_coefs, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                 int32_t layout, void *d_work, void *stream, int32_t optimize, uint64_t *d_dir);
+int mipx_op_rgb_to_jpeg_scan_packed(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
+                                    int32_t layout, int32_t quality, void *d_work, void *stream, int32_t optimize,
+                                    uint64_t *d_dir);
+size_t mipx_jpeg_scan_packed_dir_bytes(int32_t n);
+int mipx_jpeg_scan_unpack(const uint64_t *dir, int32_t n, const uint8_t *packed, size_t packed_bytes, int32_t i,
+                          size_t head, uint8_t *slot, size_t slot_bytes);
 /* The entropy decoder (see MIPX_JPEGH_HEADER_BYTES): n slots (n * mipx_jpegh_bytes(w, h, layout)
  * bytes) -> n payloads of MIPX_OP_JPEGD (n * mipx_jpegd_bytes(w, h, layout) bytes) and n uint32
  * statuses (MIPX_JPEGH_*).  mipx_jpegh_bytes works without a GPU: MIPX_JPEGH_HEADER_BYTES +

@@ -12,6 +12,7 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75     (RGB -> entropy-coded scan)
     python scripts/op_bench.py jpegcs420 --w 3840 --h 2160 --n 64 --q 75    (the entropy coder alone)
     python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75 --optimize   (with optimised Huffman tables)
+    python scripts/op_bench.py jpege420 --w 3840 --h 2160 --n 64 --q 75 --packed     (the slots packed back to back)
     python scripts/op_bench.py jpegh420 --w 3840 --h 2160 --n 64 --q 75     (entropy-coded scan -> RGB)
     python scripts/op_bench.py jpeghd420 --w 3840 --h 2160 --n 64 --q 75    (the entropy decoder alone)
     python scripts/op_bench.py jpegh420 --file tests/golden/testdata/large.jpg --n 64   (a photograph's scan)
@@ -67,6 +68,8 @@ def main():
                          "restart markers, the twin to compare with")
     ap.add_argument("--optimize", action="store_true",
                     help="jpege* / jpegcs*: optimised Huffman tables (the *_optimized calls; the slots carry the tables)")
+    ap.add_argument("--packed", action="store_true",
+                    help="jpege* / jpegcs*: the slots packed back to back behind a directory (the *_packed calls)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--ab", default="", help="KNOB=v1,v2,...: same-process A/B of a MIPX_* knob")
     ap.add_argument("--warm-ms", type=float, default=200.0, help="device-time warm-up; 0: none, one group (PMC runs)")
@@ -178,6 +181,7 @@ def main():
     if a.op in JPEGE:
         ws = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 1.0 if a.optimize else 0.0, 0.0),), dtype=torch.uint8,
                          device=dev)
+        directory = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
     if a.op in JPEGH:
         import numpy as np
         ws = torch.empty((lib.mipx_op_workspace_bytes(20, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
@@ -276,6 +280,10 @@ def main():
             return lib.mipx_op_jpegd_to_rgb_scaled(X, Y, n, w, h, layout, a.shrink, WS, WSB, sp)
         if a.op in ("jpegrt420", "jpegrt444"):
             return lib.mipx_op_jpeg_roundtrip(X, Y, n, w, h, layout, a.q, a.shrink, WS, WSB, sp)
+        if a.op in ("jpege420", "jpege444") and a.packed:
+            return lib.mipx_op_rgb_to_jpeg_scan_packed(X, Y, n, w, h, layout, a.q, WS, sp, int(a.optimize), directory.data_ptr())
+        if a.op in ("jpegcs420", "jpegcs444") and a.packed:
+            return lib.mipx_op_jpegc_to_scan_packed(X, Y, n, w, h, layout, WS, sp, int(a.optimize), directory.data_ptr())
         if a.op in ("jpege420", "jpege444"):
             if a.optimize:
                 return lib.mipx_op_rgb_to_jpeg_scan_optimized(X, Y, n, w, h, layout, a.q, WS, sp)
@@ -322,7 +330,12 @@ def main():
         line["shrink"] = a.shrink
     if not a.ab:
         ms = measure()
-        if a.op in JPEGE:   # what the slots say: the scans' mean length against the slot's capacity
+        if a.op in JPEGE and a.packed:   # what the directory says: the bytes a caller downloads of the n slots' bytes
+            offs = directory.cpu().tolist()
+            heads = [y[o:o + 16].cpu().numpy().view("<u4") for o in offs[:-1]]
+            line.update(q=a.q, optimize=a.optimize, packed=True, packed_bytes=offs[-1], slots_bytes=n * out_img,
+                        mean_length=round(sum(int(hd[0]) for hd in heads) / n, 1), statuses=sorted({int(hd[1]) for hd in heads}))
+        elif a.op in JPEGE:   # what the slots say: the scans' mean length against the slot's capacity
             head = y.view(n, out_img)[:, :16].cpu().numpy().view("<u4")
             line.update(q=a.q, optimize=a.optimize, capacity=out_img - (1104 if a.optimize else 16), mean_length=round(float(head[:, 0].mean()), 1),
                         statuses=sorted(set(head[:, 1].tolist())))
