@@ -131,6 +131,20 @@ def decode_scale(w: int, h: int, shrink: int) -> int:
 
 YCC_444 = 0   # MIPX_YCC_444: Cb and Cr at full size
 YCC_420 = 1   # MIPX_YCC_420: Cb and Cr at ceil(w / 2) x ceil(h / 2)
+YCC_422 = 3   # MIPX_YCC_422: Cb and Cr at ceil(w / 2) x h (libjpeg's h2v1); an input layout only
+
+# The samplings (h, v) of Y, Cb, Cr that the input paths take, by layout.  4:2:2 is opt-in
+# (h2v1=True below): a caller that did not ask for it gets None for such a file, as before.
+_SAMPLINGS = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}
+_SAMPLINGS_H2V1 = {**_SAMPLINGS, ((2, 1), (1, 1), (1, 1)): YCC_422}
+
+
+def _sampling_geometry(w: int, h: int, samp):
+    """Per component (wb, hb, hs, vs): its real blocks across and down and its blocks across and
+    down in one MCU; and the MCUs across and down.  samp: (hs, vs) per component."""
+    hmax, vmax = max(a for a, _ in samp), max(b for _, b in samp)
+    geo = [((-(-w * hs // hmax) + 7) // 8, (-(-h * vs // vmax) + 7) // 8, hs, vs) for hs, vs in samp]
+    return geo, -(-w // (8 * hmax)), -(-h // (8 * vmax))
 
 
 def decode_ycc(buf: bytes):
@@ -580,7 +594,7 @@ def _jpeg_segments(buf: bytes, dht=None, span=None):
     return w, h, full, qt, huff, restart, parts
 
 
-def decode_jpeg_coefs(buf: bytes):
+def decode_jpeg_coefs(buf: bytes, h2v1: bool = False):
     """A JPEG's quantised DCT coefficients as its entropy decoder has them, packed for the
     engine's MIPX_OP_JPEGD step: (payload, layout) with payload a 1-D uint8 array of the file's
     quantisation tables (Y, Cb, Cr: 64 little-endian uint16 each, natural order) and then the
@@ -590,6 +604,9 @@ def decode_jpeg_coefs(buf: bytes):
     4:2:0 in one interleaved scan, so progressive, arithmetic-coded, grey, CMYK, RGB, 4:2:2 and
     truncated files, and what is no JPEG at all (the caller then takes decode()).
 
+    h2v1=True takes 4:2:2 files too (sampling 2x1, 1x1, 1x1; layout YCC_422): chroma is
+    ceil(ceil(w / 2) / 8) blocks across and ceil(h / 8) down, the MCU is Y left, Y right, Cb, Cr.
+
     Stand-in for libjpeg's jpeg_read_coefficients: a pure-Python Huffman decoder (any tables,
     restart intervals) that looks codes up by the next 16 bits of the stream."""
     try:
@@ -597,23 +614,23 @@ def decode_jpeg_coefs(buf: bytes):
         if seg is None:
             return None
         w, h, comps, qt, huff, restart, parts = seg
-        samp = [(c[1], c[2]) for c in comps]
-        layout = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}.get(tuple(samp))
+        samp = tuple((c[1], c[2]) for c in comps)
+        layout = (_SAMPLINGS_H2V1 if h2v1 else _SAMPLINGS).get(samp)
         if layout is None:
             return None
-        geo, mw, mh = _jpegc_geometry(w, h, layout)
+        geo, mw, mh = _sampling_geometry(w, h, samp)
         if restart == 0:
             restart = mw * mh
         if len(parts) != -(-mw * mh // restart):
             return None
         # a block is at least 2 bits (a DC code and an end-of-block): a header that promises more
         # blocks than the scan can hold is damaged, and must not size the arrays below
-        if sum(s * s for _, _, s in geo) * mw * mh > 4 * sum(len(d) for d in parts):
+        if sum(hs * vs for _, _, hs, vs in geo) * mw * mh > 4 * sum(len(d) for d in parts):
             return None
-        store = [[0] * (64 * mw * mh * s * s) for _, _, s in geo]
+        store = [[0] * (64 * mw * mh * hs * vs) for _, _, hs, vs in geo]
         order = []      # the blocks of one MCU: (component, row in the MCU, column in the MCU)
-        for ci, (_, _, s) in enumerate(geo):
-            order += [(ci, by, bx) for by in range(s) for bx in range(s)]
+        for ci, (_, _, hs, vs) in enumerate(geo):
+            order += [(ci, by, bx) for by in range(vs) for bx in range(hs)]
         dc = [huff[c[4]] for c in comps]
         ac = [huff[c[5]] for c in comps]
         zz = ZIGZAG
@@ -626,9 +643,9 @@ def decode_jpeg_coefs(buf: bytes):
             for mcu in range(mcu, min(mcu + restart, mw * mh)):
                 my, mx = divmod(mcu, mw)
                 for ci, by, bx in order:
-                    s = geo[ci][2]
+                    hs, vs = geo[ci][2:]
                     out = store[ci]
-                    base = 64 * ((my * s + by) * mw * s + mx * s + bx)
+                    base = 64 * ((my * vs + by) * mw * hs + mx * hs + bx)
                     lut = dc[ci]
                     k = 0
                     while k < 64:
@@ -671,8 +688,8 @@ def decode_jpeg_coefs(buf: bytes):
         if mcu != mw * mh:
             return None
         body = []
-        for (wb, hb, s), flat in zip(geo, store):
-            a = np.array(flat, dtype=np.int64).reshape(mh * s, mw * s, 64)[:hb, :wb]
+        for (wb, hb, hs, vs), flat in zip(geo, store):
+            a = np.array(flat, dtype=np.int64).reshape(mh * vs, mw * hs, 64)[:hb, :wb]
             if a.size and (a.min() < -32768 or a.max() > 32767):
                 return None
             body.append(a.astype("<i2").ravel())
@@ -687,7 +704,7 @@ JPEGH_HEADER_BYTES = 1504   # MIPX_JPEGH_HEADER_BYTES
 JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
 
 
-def jpeg_huff_slot(buf: bytes, restart: bool = False):
+def jpeg_huff_slot(buf: bytes, restart: bool = False, h2v1: bool = False):
     """A JPEG's entropy-coded scan as the file has it, packed for the engine's entropy decoder
     (MIPX_JPEGH_HEADER_BYTES in include/mipx.h): (slot, layout) with slot a 1-D uint8 array of
     the scan's length, the quantisation tables of Y, Cb, Cr, the components' Huffman table
@@ -699,7 +716,9 @@ def jpeg_huff_slot(buf: bytes, restart: bool = False):
 
     restart=True takes files with a restart interval (DRI) too: the interval, in MCUs, goes into
     the header at offset 4 (0 for a file without one) and the scan is the file's bytes between the
-    SOS segment and FF D9 as they are, restart markers included; the engine checks the markers."""
+    SOS segment and FF D9 as they are, restart markers included; the engine checks the markers.
+
+    h2v1=True takes 4:2:2 files too, as decode_jpeg_coefs does (layout YCC_422)."""
     try:
         buf = bytes(buf)
         dht, span = {}, []
@@ -708,15 +727,15 @@ def jpeg_huff_slot(buf: bytes, restart: bool = False):
             return None
         w, h, comps, qt, _, interval, parts = seg
         samp = tuple((c[1], c[2]) for c in comps)
-        layout = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}.get(samp)
+        layout = (_SAMPLINGS_H2V1 if h2v1 else _SAMPLINGS).get(samp)
         if layout is None:
             return None
         if not restart and (interval != 0 or len(parts) != 1):
             return None
         if any(c[4] > 1 or (c[5] & 15) > 1 for c in comps):
             return None
-        geo, _, _ = _jpegc_geometry(w, h, layout)
-        cap = 128 * sum(wb * hb for wb, hb, _ in geo)
+        geo, _, _ = _sampling_geometry(w, h, samp)
+        cap = 128 * sum(g[0] * g[1] for g in geo)
         scan = buf[span[0]:span[1]] if restart else parts[0]
         if len(scan) > cap:
             return None

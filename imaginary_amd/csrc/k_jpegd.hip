@@ -139,13 +139,13 @@ __global__ void __launch_bounds__(256) k_jpegd(const JpegdArgs a) {
 // The caller has checked that an image's payload and its RGB are below 2^32 bytes, so every
 // byte offset inside an image fits 32 bits.
 int jpegd_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, hipStream_t st) {
-    const bool sub = layout == MIPX_YCC_420;
+    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
     JpegdArgs a;
     a.in = d_in, a.out = d_planes;
     a.in_img = static_cast<long long>(mipx_jpegd_bytes(w, h, layout));
     a.out_img = static_cast<long long>(mipx_ycc_bytes(w, h, layout));
     a.pw[0] = w, a.ph[0] = h;
-    a.pw[1] = sub ? (static_cast<uint32_t>(w) + 1u) / 2u : w;
+    a.pw[1] = sub || h2v1 ? (static_cast<uint32_t>(w) + 1u) / 2u : w;
     a.ph[1] = sub ? (static_cast<uint32_t>(h) + 1u) / 2u : h;
     long long total = 0;
     for (int c = 0; c < 2; ++c) {
@@ -167,7 +167,10 @@ int jpegd_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, 
 // gets an N x N inverse DCT of its 8 x 8 blocks, which then tile its plane at pitch N.  Y and
 // 4:4:4 chroma take N = 8 / s; 4:2:0 chroma takes N = 16 / s, so all three planes come out at
 // ceil(W / s) x ceil(H / s) and there is no upsampling: the output is three equal planes, the
-// packed MIPX_YCC_444 layout k_ycc.hip takes.  Dequantisation, pass order, the int16 saturation
+// packed MIPX_YCC_444 layout k_ycc.hip takes.  4:2:2 chroma takes N = 8 / s like Y (its vertical
+// ratio is 1, and jdmaster.c enlarges a component's N only when both ratios allow it): it comes
+// out ceil(H / s) high and ceil(ceil(W / s) / 2) wide, so the output is the packed MIPX_YCC_422
+// planes of the decoded size, which k_ycc.hip then upsamples.  Dequantisation, pass order, the int16 saturation
 // after pass 1 and the final clamp are k_jpegd's; with DS(v, S) = (v + (1 << (S - 1))) >> S:
 //   N = 8: the pass above, S = 11 then 18
 //   N = 4: on i0 i1 i2 i3 i5 i6 i7 (i4 is never read), S = 12 then 19:
@@ -205,8 +208,9 @@ struct JpegdsArgs {
     const u8 *in;
     u8 *out;
     long long in_img, out_img;  // bytes per image
-    uint32_t pw, ph;            // size of every plane: ceil(W / s) x ceil(H / s)
     // [0]: Y, [1]: Cb and Cr
+    uint32_t pw[2], ph;         // plane size: ceil(W / s) x ceil(H / s); 4:2:2 chroma half as wide
+    uint32_t plane_off[3];      // byte offset of each component's plane in an image's output
     uint32_t nidct[2];          // 8, 4, 2 or 1
     uint32_t wb[2], hb[2];      // real blocks across and down (the file's)
     uint32_t runs[2];           // runs of 256 / N blocks in one block row (N > 1)
@@ -309,10 +313,10 @@ __global__ void __launch_bounds__(256) k_jpegds(const JpegdsArgs a) {
         if (g >= a.groups[1]) g -= a.groups[1], comp = 2;
     }
     const uint32_t c = comp ? 1u : 0u;
-    const uint32_t n = a.nidct[c], wb = a.wb[c], pw = a.pw, ph = a.ph;
+    const uint32_t n = a.nidct[c], wb = a.wb[c], pw = a.pw[c], ph = a.ph;
     const u8 *coefs = in + MIPX_JPEGD_HEADER_BYTES + a.coef_off[comp];
     const u8 *qt = in + comp * 128u;
-    u8 *plane = out + comp * (pw * ph);
+    u8 *plane = out + a.plane_off[comp];
     if (n == 1u) {  // the plane is the block grid: sample i is the DC term of block i
         const uint32_t total = wb * a.hb[c];
         const uint32_t i0 = (g * 256u + threadIdx.x) * kDcPerLane;
@@ -347,21 +351,23 @@ __global__ void __launch_bounds__(256) k_jpegds(const JpegdsArgs a) {
 // w x h is the file's size.  The caller has checked that the payload and the RGB at the output
 // size are below 2^32 bytes, and that shrink is 2, 4 or 8.
 int jpegds_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, int shrink, hipStream_t st) {
-    const bool sub = layout == MIPX_YCC_420;
+    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
     const uint32_t s = static_cast<uint32_t>(shrink);
     JpegdsArgs a;
     a.in = d_in, a.out = d_planes;
     a.in_img = static_cast<long long>(mipx_jpegd_bytes(w, h, layout));
-    a.pw = (static_cast<uint32_t>(w) + s - 1u) / s, a.ph = (static_cast<uint32_t>(h) + s - 1u) / s;
-    a.out_img = 3ll * a.pw * a.ph;
-    const uint32_t cw[2] = {static_cast<uint32_t>(w), sub ? (static_cast<uint32_t>(w) + 1u) / 2u : w};
+    a.pw[0] = (static_cast<uint32_t>(w) + s - 1u) / s, a.ph = (static_cast<uint32_t>(h) + s - 1u) / s;
+    a.pw[1] = h2v1 ? (a.pw[0] + 1u) / 2u : a.pw[0];
+    a.plane_off[0] = 0u, a.plane_off[1] = a.pw[0] * a.ph, a.plane_off[2] = a.plane_off[1] + a.pw[1] * a.ph;
+    a.out_img = static_cast<long long>(a.plane_off[2]) + a.pw[1] * a.ph;
+    const uint32_t cw[2] = {static_cast<uint32_t>(w), sub || h2v1 ? (static_cast<uint32_t>(w) + 1u) / 2u : w};
     const uint32_t ch[2] = {static_cast<uint32_t>(h), sub ? (static_cast<uint32_t>(h) + 1u) / 2u : h};
     a.nidct[0] = 8u / s, a.nidct[1] = sub ? 16u / s : 8u / s;
     long long total = 0;
     for (int c = 0; c < 2; ++c) {
         a.wb[c] = (cw[c] + 7u) / 8u, a.hb[c] = (ch[c] + 7u) / 8u;
         if (a.nidct[c] == 1u) {  // linear over the block grid, which is the plane
-            if (a.wb[c] != a.pw || a.hb[c] != a.ph) return MIPX_EINVAL;
+            if (a.wb[c] != a.pw[c] || a.hb[c] != a.ph) return MIPX_EINVAL;
             const uint32_t per = 256u * kDcPerLane;
             a.runs[c] = 1u;
             a.groups[c] = static_cast<uint32_t>((static_cast<unsigned long long>(a.wb[c]) * a.hb[c] + per - 1u) / per);

@@ -6,8 +6,10 @@
 // A Huffman stream has no known codeword boundaries, so the decoders are started speculatively and
 // synchronise: the unstuffed stream is cut into subsequences of kJpeghSub bytes, one lane each, and
 // sequences of kJpeghSeq subsequences, one workgroup each.  The state a decoder needs at a bit is
-// (block index inside the MCU, zigzag index).  Every dependency between workgroups is a launch
-// boundary on the stream; no kernel waits for another workgroup; every loop has a bound.
+// (block index inside the MCU, zigzag index); an MCU is 3 blocks in 4:4:4, 6 in 4:2:0 and 4 in
+// 4:2:2 (Y left, Y right, Cb, Cr; the chroma grid is then the MCU grid).  Every dependency
+// between workgroups is a launch boundary on the stream; no kernel waits for another workgroup;
+// every loop has a bound.
 //   memset             the statuses, the per-image records, the payloads (zero coefficients)
 //   k_jpegh_ffcount    FF 00 pairs per kChunk bytes of the stuffed scan; FF + anything else: BAD
 //   k_jpegh_prep       one workgroup per image: the scan of those counts, the unstuffed length,
@@ -68,6 +70,9 @@ static_assert(kPending != MIPX_JPEGH_OK && kPending != MIPX_JPEGH_UNSYNCED && kP
 // them, and one more so that the lanes of a wave, each at its own bit, read 64 different banks
 constexpr uint32_t kStagePitch = kJpeghSub / 4u + 3u;
 static_assert(kJpeghSub % 4 == 0 && (kStagePitch & 1u) == 1u, "an odd pitch spreads the lanes over the banks");
+// blocks of an MCU: Y Cb Cr; Y00 Y01 Y10 Y11 Cb Cr; 4:2:2's Y0 Y1 Cb Cr
+template <int LAYOUT>
+constexpr uint32_t per_mcu() { return LAYOUT == MIPX_YCC_444 ? 3u : LAYOUT == MIPX_YCC_422 ? 4u : 6u; }
 constexpr uint32_t kTablesOff = 416, kTableBytes = 272, kSelOff = 400, kQuantOff = 16;
 static_assert(kLanes == 256, "block_scan sums four waves");
 
@@ -313,6 +318,9 @@ __device__ __forceinline__ void load_tables(const u8 *slot, Huff &H) {
         if (LAYOUT == MIPX_YCC_444) {
             H.dcsel = d[0] | d[1] << 1 | d[2] << 2;
             H.acsel = c[0] | c[1] << 1 | c[2] << 2;
+        } else if (LAYOUT == MIPX_YCC_422) {
+            H.dcsel = d[0] * 3u | d[1] << 2 | d[2] << 3;
+            H.acsel = c[0] * 3u | c[1] << 2 | c[2] << 3;
         } else {
             H.dcsel = d[0] * 15u | d[1] << 4 | d[2] << 5;
             H.acsel = c[0] * 15u | c[1] << 4 | c[2] << 5;
@@ -384,7 +392,7 @@ struct Step {
 // 1..31 bits and leaves a state.
 template <int LAYOUT>
 __device__ __forceinline__ Step step_bits(State &s, const Huff &H, const uint32_t v) {
-    constexpr uint32_t kPerMcu = LAYOUT == MIPX_YCC_444 ? 3u : 6u;
+    constexpr uint32_t kPerMcu = per_mcu<LAYOUT>();
     Step r;
     r.error = false, r.value = false, r.block_end = false, r.k = 0, r.coef = 0;
     const uint32_t t = s.k == 0u ? (H.dcsel >> s.b & 1u) : 2u + (H.acsel >> s.b & 1u);
@@ -562,6 +570,17 @@ __device__ __forceinline__ uint32_t block_dst(const JpeghArgs &a, uint32_t cur, 
         *comp = c;
         return (c == 0u ? 0u : c == 1u ? a.cb_off : a.cr_off) + m * 128u;
     }
+    if (LAYOUT == MIPX_YCC_422) {  // the chroma grid is the MCU grid; Y block j is the MCU's column j
+        const uint32_t m = cur / 4u, j = cur - 4u * m;
+        if (j >= 2u) {
+            *comp = j - 1u;
+            return (j == 2u ? a.cb_off : a.cr_off) + m * 128u;
+        }
+        *comp = 0u;
+        const uint32_t my = m / a.mw, mx = m - my * a.mw;
+        const uint32_t bx = 2u * mx + j;
+        return bx < a.ywb ? (my * a.ywb + bx) * 128u : kNone;
+    }
     const uint32_t m = cur / 6u, j = cur - 6u * m;
     if (j >= 4u) {
         *comp = j - 3u;
@@ -630,6 +649,10 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_write(const JpeghArgs a) {
 template <int LAYOUT>
 __device__ __forceinline__ uint32_t comp_of(uint32_t cur) {
     if (LAYOUT == MIPX_YCC_444) return cur % 3u;
+    if (LAYOUT == MIPX_YCC_422) {
+        const uint32_t j = cur % 4u;
+        return j < 2u ? 0u : j - 1u;
+    }
     const uint32_t j = cur % 6u;
     return j < 4u ? 0u : j - 3u;
 }
@@ -755,7 +778,7 @@ __global__ void __launch_bounds__(kLanes) k_jpegr_index(const JpeghArgs a) {
 // takes a bit or more, so the loop ends within the interval's bits.
 template <int LAYOUT>
 __global__ void __launch_bounds__(kLanes) k_jpegr_decode(const JpeghArgs a) {
-    constexpr uint32_t kPerMcu = LAYOUT == MIPX_YCC_444 ? 3u : 6u;
+    constexpr uint32_t kPerMcu = per_mcu<LAYOUT>();
     __shared__ Huff H;
     const uint32_t img = blockIdx.y, tid = threadIdx.x;
     if (a.status[img] != kPending) return;  // nothing changes it during this launch
@@ -839,7 +862,7 @@ __global__ void __launch_bounds__(kLanes) k_jpegr_decode(const JpeghArgs a) {
 int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, int w, int h, int layout, u8 *work,
                  hipStream_t st) {
     const JpeghWork W(n, w, h);
-    const bool sub = layout == MIPX_YCC_420;
+    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
     JpeghArgs a;
     a.slots = d_slots, a.payloads = d_payloads, a.status = d_status;
     a.info = reinterpret_cast<JpeghInfo *>(work + W.info);
@@ -860,12 +883,12 @@ int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, i
     a.chunks = static_cast<uint32_t>(W.chunks), a.seqs = static_cast<uint32_t>(W.seqs), a.tiles = static_cast<uint32_t>(W.tiles);
     a.wblocks = static_cast<uint32_t>(W.blocks);
     a.ywb = (static_cast<uint32_t>(w) + 7u) / 8u, a.yhb = (static_cast<uint32_t>(h) + 7u) / 8u;
-    const uint32_t cwb = sub ? ((static_cast<uint32_t>(w) + 1u) / 2u + 7u) / 8u : a.ywb;
+    const uint32_t cwb = sub || h2v1 ? ((static_cast<uint32_t>(w) + 1u) / 2u + 7u) / 8u : a.ywb;
     const uint32_t chb = sub ? ((static_cast<uint32_t>(h) + 1u) / 2u + 7u) / 8u : a.yhb;
     a.mw = cwb;
     a.cb_off = a.ywb * a.yhb * 128u;
     a.cr_off = a.cb_off + cwb * chb * 128u;
-    const unsigned long long blocks = static_cast<unsigned long long>(cwb) * chb * (sub ? 6u : 3u);
+    const unsigned long long blocks = static_cast<unsigned long long>(cwb) * chb * (sub ? 6u : h2v1 ? 4u : 3u);
     a.blocks = static_cast<uint32_t>(blocks);
     a.mcus = cwb * chb;
     // the grids of this image: by its own capacity, inside the workspace's strides
@@ -891,26 +914,31 @@ int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, i
     hipLaunchKernelGGL(k_jpegr_index, by_index, threads, 0, st, a);
     if ((e = launch_check("k_jpegr_index"))) return e;
     if (sub) hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_420>, by_interval, threads, 0, st, a);
+    else if (h2v1) hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_422>, by_interval, threads, 0, st, a);
     else hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_444>, by_interval, threads, 0, st, a);
     if ((e = launch_check("k_jpegr_decode"))) return e;
     hipLaunchKernelGGL(k_jpegh_unstuff, by_chunk, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_unstuff"))) return e;
     for (uint32_t round = 0; round <= kJpeghRounds; ++round) {
         if (sub) hipLaunchKernelGGL(k_jpegh_sync<MIPX_YCC_420>, by_seq, threads, 0, st, a, round);
+        else if (h2v1) hipLaunchKernelGGL(k_jpegh_sync<MIPX_YCC_422>, by_seq, threads, 0, st, a, round);
         else hipLaunchKernelGGL(k_jpegh_sync<MIPX_YCC_444>, by_seq, threads, 0, st, a, round);
         if ((e = launch_check("k_jpegh_sync"))) return e;
     }
     hipLaunchKernelGGL(k_jpegh_place, by_image, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_place"))) return e;
     if (sub) hipLaunchKernelGGL(k_jpegh_write<MIPX_YCC_420>, by_seq, threads, 0, st, a);
+    else if (h2v1) hipLaunchKernelGGL(k_jpegh_write<MIPX_YCC_422>, by_seq, threads, 0, st, a);
     else hipLaunchKernelGGL(k_jpegh_write<MIPX_YCC_444>, by_seq, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_write"))) return e;
     if (sub) hipLaunchKernelGGL(k_jpegh_dcsum<MIPX_YCC_420>, by_tile, threads, 0, st, a);
+    else if (h2v1) hipLaunchKernelGGL(k_jpegh_dcsum<MIPX_YCC_422>, by_tile, threads, 0, st, a);
     else hipLaunchKernelGGL(k_jpegh_dcsum<MIPX_YCC_444>, by_tile, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_dcsum"))) return e;
     hipLaunchKernelGGL(k_jpegh_dcscan, by_image, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_dcscan"))) return e;
     if (sub) hipLaunchKernelGGL(k_jpegh_dcwrite<MIPX_YCC_420>, by_tile, threads, 0, st, a);
+    else if (h2v1) hipLaunchKernelGGL(k_jpegh_dcwrite<MIPX_YCC_422>, by_tile, threads, 0, st, a);
     else hipLaunchKernelGGL(k_jpegh_dcwrite<MIPX_YCC_444>, by_tile, threads, 0, st, a);
     return launch_check("k_jpegh_dcwrite");
 }

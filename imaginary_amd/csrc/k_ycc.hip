@@ -4,6 +4,11 @@
 //     cy = y >> 1, cx = x >> 1; ny = cy - 1 for even y, cy + 1 for odd y, nx alike, clamped
 //     s(c) = 3 C[cy][c] + C[ny][c];  c(x, y) = (3 s(cx) + s(nx) + (x even ? 8 : 7)) >> 4
 //     cw <= 2: plain replication, c(x, y) = C[cy][cx] (the same expression with ny = cy, nx = cx)
+//   4:2:2 chroma (jdsample.c h2v1_fancy_upsample, chosen when cw > 2), C an h x cw plane, no
+//   vertical term (PARITY_ASSUMPTIONS.md row 25):
+//     cx = x >> 1; nx = cx - 1 for even x, cx + 1 for odd x, clamped
+//     c(x, y) = (3 C[y][cx] + C[y][nx] + (x even ? 1 : 2)) >> 2
+//     cw <= 2, and at every width behind a 1 / 8 decode (the launch's `replicate`): c(x, y) = C[y][cx]
 //   conversion (jdcolor.c), int32, arithmetic shifts, cb = Cb - 128, cr = Cr - 128:
 //     R = clamp(Y + ((91881 cr + 32768) >> 16))
 //     G = clamp(Y + ((-22554 cb - 46802 cr + 32768) >> 16))
@@ -17,7 +22,9 @@
 // store, so a wave reads 256 and writes 768 contiguous bytes per row.  In 4:2:0 a lane does
 // output rows 2j - 1 and 2j, which read the same two chroma rows j - 1 and j (weights 3 : 1
 // and 1 : 3), so the four chroma dwords serve 8 pixels; it walks a few such row pairs, keeping
-// chroma row j for the next one and loading ahead of the arithmetic.  All accesses are plain
+// chroma row j for the next one and loading ahead of the arithmetic.  4:2:2 is the same lane
+// without the row pairing: one Y dword and one dword per chroma plane make the 4 pixels of one
+// row, and a lane walks a few rows with the next row's loads ahead.  All accesses are plain
 // unaligned dword ones: rows, planes and images start on any byte (w * h may be odd), and when
 // they happen to be dword-aligned (any w that is a multiple of 4) so is every access.  A row's
 // first and last lanes gather the same four chroma columns byte by byte with clamped indices
@@ -41,8 +48,8 @@ struct YccArgs {
     long long in_img, out_img;  // bytes per image
     uint32_t w, h, cw, ch;
     uint32_t npix, cpix;        // w * h, cw * ch
-    uint32_t gx;                // 4:2:0: blocks across one image
-    int rep;                    // 4:2:0 with cw <= 2: chroma replicated
+    uint32_t gx;                // 4:2:0, 4:2:2: blocks across one image
+    int rep;                    // 4:2:0, 4:2:2: chroma replicated (cw <= 2; 4:2:2 also on request)
 };
 
 __device__ __forceinline__ uint32_t ld32(const u8 *p) {
@@ -105,6 +112,16 @@ __device__ __forceinline__ void ycc_up4(uint32_t near, uint32_t far, int c[4]) {
     c[3] = (3 * s[2] + s[3] + 7) >> 4;
 }
 
+// h2v1 fancy upsample of output columns x0 .. x0 + 3 (x0 even) of one row: `row` holds chroma
+// columns cx0 - 1 .. cx0 + 2 of that row; rep: replicated instead
+__device__ __forceinline__ void ycc_up4h(uint32_t row, int rep, int c[4]) {
+    const int s0 = byte_of(row, 0), s1 = byte_of(row, 1), s2 = byte_of(row, 2), s3 = byte_of(row, 3);
+    c[0] = rep ? s1 : (3 * s1 + s0 + 1) >> 2;
+    c[1] = rep ? s1 : (3 * s1 + s2 + 2) >> 2;
+    c[2] = rep ? s2 : (3 * s2 + s1 + 1) >> 2;
+    c[3] = rep ? s2 : (3 * s2 + s3 + 2) >> 2;
+}
+
 // one output pixel by the formulas at the top, every index clamped (edges, cw <= 2, tails)
 template <int LAYOUT>
 __device__ void ycc_pixel(const YccArgs &a, const u8 *in, u8 *out, uint32_t x, uint32_t y) {
@@ -113,6 +130,14 @@ __device__ void ycc_pixel(const YccArgs &a, const u8 *in, u8 *out, uint32_t x, u
     int cb, cr;
     if (LAYOUT == MIPX_YCC_444) {
         cb = pcb[p], cr = pcr[p];
+    } else if (LAYOUT == MIPX_YCC_422) {
+        const uint32_t cx = x >> 1;
+        uint32_t nx = (x & 1u) ? min(cx + 1u, a.cw - 1u) : (cx ? cx - 1u : 0u);
+        if (a.rep) nx = cx;
+        const uint32_t cc = y * a.cw + cx, cn = y * a.cw + nx;
+        const int bias = (x & 1u) ? 2 : 1;
+        cb = (3 * pcb[cc] + pcb[cn] + bias) >> 2;
+        cr = (3 * pcr[cc] + pcr[cn] + bias) >> 2;
     } else {
         const uint32_t cy = y >> 1, cx = x >> 1;
         uint32_t ny = (y & 1u) ? min(cy + 1u, a.ch - 1u) : (cy ? cy - 1u : 0u);
@@ -209,6 +234,45 @@ __global__ void __launch_bounds__(256) k_ycc420(const YccArgs a) {
     }
 }
 
+// 4:2:2.  Block = 4 waves; wave t walks kYcc422Rows rows, its lanes 64 consecutive groups of 4
+// columns.  A row reads its own chroma row only, so each step loads one chroma dword per plane and
+// one Y dword, and it loads them for row y + 1 before it computes row y.
+constexpr uint32_t kYcc422Rows = 8;
+
+__global__ void __launch_bounds__(256) k_ycc422(const YccArgs a) {
+    const u8 *in = a.in + blockIdx.y * a.in_img;
+    u8 *out = a.out + blockIdx.y * a.out_img;
+    const uint32_t by = blockIdx.x / a.gx, bx = blockIdx.x - by * a.gx;
+    // threadIdx.y is the wave: y and the row addresses made from it are scalar
+    const uint32_t g = bx * 64u + threadIdx.x;
+    const uint32_t y0 = __builtin_amdgcn_readfirstlane((by * 4u + threadIdx.y) * kYcc422Rows);
+    const uint32_t x0 = 4u * g, yend = min(y0 + kYcc422Rows, a.h);
+    if (x0 >= a.w || y0 >= yend) return;
+    if (a.cw <= 2u) {  // so w <= 4: one lane per row
+        for (uint32_t y = y0; y < yend; ++y)
+            for (uint32_t x = x0; x < a.w; ++x) ycc_pixel<MIPX_YCC_422>(a, in, out, x, y);
+        return;
+    }
+    const u8 *pcb = in + a.npix, *pcr = pcb + a.cpix;
+    const bool interior = g >= 1u && 2u * g + 2u <= a.cw - 1u;
+    const uint32_t px = min(4u, a.w - x0);  // pixels of this lane
+    uint32_t bw = ycc_chroma4(pcb + y0 * a.cw, g, a.cw, interior), rw = ycc_chroma4(pcr + y0 * a.cw, g, a.cw, interior);
+    uint32_t yw = ycc_luma4(in + y0 * a.w + x0, px);
+    for (uint32_t y = y0; y < yend; ++y) {
+        uint32_t nbw = 0u, nrw = 0u, nyw = 0u;
+        if (y + 1u < yend) {  // the next row's loads first
+            nbw = ycc_chroma4(pcb + (y + 1u) * a.cw, g, a.cw, interior), nrw = ycc_chroma4(pcr + (y + 1u) * a.cw, g, a.cw, interior);
+            nyw = ycc_luma4(in + (y + 1u) * a.w + x0, px);
+        }
+        int cb[4], cr[4];
+        uint32_t d[3];
+        ycc_up4h(bw, a.rep, cb), ycc_up4h(rw, a.rep, cr);
+        ycc_rgb4(yw, cb, cr, d);
+        ycc_store(out + 3u * (y * a.w + x0), d, 3u * px);
+        bw = nbw, rw = nrw, yw = nyw;
+    }
+}
+
 // 4:4:4: the three planes have the image's shape, so the walk is flat over w * h pixels, 4
 // per lane and kYcc444Unroll groups per lane with their loads issued together
 constexpr int kYcc444Unroll = 2;
@@ -247,22 +311,30 @@ __global__ void __launch_bounds__(256) k_ycc444(const YccArgs a) {
 
 }  // namespace
 
-int ycc_launch(const u8 *d_in, u8 *d_out, int n, int w, int h, int layout, hipStream_t st) {
+int ycc_launch(const u8 *d_in, u8 *d_out, int n, int w, int h, int layout, hipStream_t st, bool replicate) {
     const long long npix = static_cast<long long>(w) * h;
     if (npix * 3 > 0xffffffffLL) {  // byte offsets inside an image are 32-bit
         set_error("ycc to rgb: image %dx%d too large (3 * w * h >= 2^32)", w, h);
         return MIPX_EUNSUPPORTED;
     }
-    const bool sub = layout == MIPX_YCC_420;
+    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
     YccArgs a;
     a.in = d_in, a.out = d_out;
     a.w = w, a.h = h;
-    a.cw = sub ? (w + 1) / 2 : w, a.ch = sub ? (h + 1) / 2 : h;
+    a.cw = sub || h2v1 ? (w + 1) / 2 : w, a.ch = sub ? (h + 1) / 2 : h;
     a.npix = static_cast<uint32_t>(npix);
     a.cpix = a.cw * a.ch;
     a.in_img = npix + 2LL * a.cpix, a.out_img = npix * 3;
-    a.rep = sub && a.cw <= 2;
+    a.rep = (sub && a.cw <= 2) || (h2v1 && (a.cw <= 2 || replicate));
     a.gx = 1;
+    if (h2v1) {
+        const long long groups = (static_cast<long long>(w) + 3) / 4;
+        const long long gx = (groups + 63) / 64, gy = (static_cast<long long>(h) + 4 * kYcc422Rows - 1) / (4 * kYcc422Rows);
+        if (!grid_ok(gx * gy)) return MIPX_EUNSUPPORTED;
+        a.gx = static_cast<uint32_t>(gx);
+        hipLaunchKernelGGL(k_ycc422, dim3(static_cast<unsigned>(gx * gy), n), dim3(64, 4), 0, st, a);
+        return launch_check("k_ycc422");
+    }
     if (sub) {
         const long long groups = (static_cast<long long>(w) + 3) / 4, pairs = h / 2 + 1;
         const long long gx = (groups + 63) / 64, gy = (pairs + 4 * kYccPairs - 1) / (4 * kYccPairs);

@@ -199,14 +199,16 @@ int watermark_launch(const uint8_t *base, const uint8_t *wm, uint8_t *out, int n
 // k_textmark.hip: the rendered text mask (tw x th x 1) tiled and blended in; 1 or 3 bands -> 3
 int textmark_launch(const uint8_t *in, const uint8_t *mask, uint8_t *out, int n, int w, int h, int bands, int tw,
                     int th, int margin, float opacity, const int *colour, hipStream_t st);
-// k_ycc.hip: packed JPEG planes (MIPX_YCC_*) -> RGB
-int ycc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, hipStream_t st);
+// k_ycc.hip: packed JPEG planes (MIPX_YCC_*) -> RGB.  replicate: 4:2:2 chroma is replicated at every
+// width, as libjpeg does behind its 1 / 8 decode; the other layouts ignore it
+int ycc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, hipStream_t st,
+               bool replicate = false);
 // k_jpegc.hip: RGB -> the quantised DCT coefficients of a JPEG (MIPX_YCC_* layout, quality 1..100)
 int jpegc_launch(const uint8_t *in, uint8_t *out, int n, int w, int h, int layout, int quality, hipStream_t st);
 // k_jpegd.hip: quantisation tables + quantised coefficients (MIPX_OP_JPEGD) -> the packed planes ycc_launch takes
 int jpegd_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, hipStream_t st);
 // the same payload of a w x h file at 1/shrink (2, 4, 8) -> three planes of ceil(w / shrink) x ceil(h / shrink),
-// packed as MIPX_YCC_444
+// packed as MIPX_YCC_444; of a 4:2:2 file the planes of that size packed as MIPX_YCC_422
 int jpegds_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int layout, int shrink, hipStream_t st);
 // k_jpegrt.hip: RGB -> the planes ycc_launch takes of the JPEG of each image at `quality`, decoded at 1/shrink
 // (1, 2, 4, 8): packed as `layout` at full size, as three ceil(w / shrink) x ceil(h / shrink) planes otherwise
@@ -222,7 +224,7 @@ int jpege_launch(const uint8_t *coefs, uint8_t *out, int n, int w, int h, int la
                  hipStream_t st, unsigned long long *d_dir = nullptr);
 // The coder's workspace, sized without the layout (both fit): byte offsets of its parts, each a multiple
 // of 256, and the total.  Per image: cap = 384 ceil(w / 8) ceil(h / 8) bytes, the 4:4:4 coefficients;
-// blocks = the scan's blocks, dummy ones included, of whichever layout has more.
+// blocks = the scan's blocks, dummy ones included, of whichever output layout has more.
 constexpr int kJpegeTile = 256;     // scan blocks per workgroup of the count and pack kernels
 constexpr int kJpegeChunk = 1024;   // stream bytes per workgroup of the stuffing kernels
 struct JpegeWork {
@@ -270,6 +272,8 @@ constexpr int kJpeghSeq = 256;   // lanes, so subsequences, per workgroup: a seq
 constexpr int kJpeghRounds = 2;  // launches that carry states across sequences, after the first
 // The decoder's workspace, sized without the layout like JpegeWork: byte offsets of its parts, each a
 // multiple of 256, and the total.  The statuses lead, so a plan's caller finds them at the head.
+// blocks is the most of the three input layouts: 4:2:2's 4 ceil(ywb / 2) yhb passes the other two
+// where ywb = 1 and yhb is even.
 struct JpeghWork {
     size_t cap, blocks, tiles, chunks, seqs, sstride;
     size_t status;      // n u32: MIPX_JPEGH_* per image
@@ -294,6 +298,7 @@ struct JpeghWork {
         const size_t mcus = ((ywb + 1) / 2) * ((yhb + 1) / 2), N = static_cast<size_t>(n);
         cap = 384 * ywb * yhb;
         blocks = 3 * ywb * yhb > 6 * mcus ? 3 * ywb * yhb : 6 * mcus;
+        if (4 * ((ywb + 1) / 2) * yhb > blocks) blocks = 4 * ((ywb + 1) / 2) * yhb;
         tiles = (blocks + kJpeghSeq - 1) / kJpeghSeq;
         chunks = (cap + 4 * kJpeghSeq - 1) / (4 * kJpeghSeq);
         seqs = (cap + kJpeghSub * kJpeghSeq - 1) / (kJpeghSub * kJpeghSeq);
@@ -335,6 +340,12 @@ size_t plan_input_bytes(const mipx_plan *p);
 size_t plan_output_bytes(const mipx_plan *p);
 // whether a w x h scan is inside the optimised tables' rule: 64 x its blocks < 10^9
 bool jpeg_opt_in_range(int w, int h, int layout);
+
+// the layouts the engine reads (planes, coefficients, scans), and those it writes a JPEG in
+inline bool ycc_input_layout(int layout) {
+    return layout == MIPX_YCC_444 || layout == MIPX_YCC_420 || layout == MIPX_YCC_422;
+}
+inline bool ycc_output_layout(int layout) { return layout == MIPX_YCC_444 || layout == MIPX_YCC_420; }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -156,8 +156,7 @@ int mipx_op_text_watermark(const uint8_t *d_in, const uint8_t *d_mask, uint8_t *
 
 int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                        void *stream) {
-    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
-        return MIPX_EINVAL;
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_input_layout(layout)) return MIPX_EINVAL;
     return ycc_launch(d_in, d_out, n, w, h, layout, as_stream(stream));
 }
 
@@ -263,8 +262,7 @@ int mipx_op_rgb_to_jpeg_scan_packed(const uint8_t *d_in, uint8_t *d_out, int32_t
 // The checks the three entropy-decoder calls share; *work: the workspace.
 static int jpegh_check(const char *what, const void *d_slots, const void *d_out, const uint32_t *d_status, int32_t n,
                        int32_t w, int32_t h, int32_t layout, void *d_ws, size_t ws_bytes) {
-    if (!d_slots || !d_out || !d_status || !d_ws || !geom_ok(n, w, h, 3) ||
-        (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
+    if (!d_slots || !d_out || !d_status || !d_ws || !geom_ok(n, w, h, 3) || !ycc_input_layout(layout))
         return MIPX_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_ws) & 15u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
         set_error("%s: the workspace is not 16-byte aligned, or the statuses are not 4-byte aligned", what);
@@ -311,8 +309,7 @@ int mipx_op_jpegh_to_rgb(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_sta
 
 int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                          void *d_ws, size_t ws_bytes, void *stream) {
-    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
-        return MIPX_EINVAL;
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_input_layout(layout)) return MIPX_EINVAL;
     // byte offsets inside an image are 32-bit in both kernels
     if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
         set_error("jpeg coefficients to rgb: image %dx%d too large (an image's bytes >= 2^32)", w, h);
@@ -332,7 +329,7 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
 int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t file_w, int32_t file_h,
                                 int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes, void *stream) {
     if (shrink == 1) return mipx_op_jpegd_to_rgb(d_in, d_out, n, file_w, file_h, layout, d_ws, ws_bytes, stream);
-    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
+    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || !ycc_input_layout(layout) ||
         (shrink != 2 && shrink != 4 && shrink != 8))
         return MIPX_EINVAL;
     const int ow = static_cast<int>((static_cast<long long>(file_w) + shrink - 1) / shrink);
@@ -348,9 +345,12 @@ int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, 
                   op_workspace_bytes(MIPX_OP_JPEGD, n, ow, oh, 3, 0, 0));
         return MIPX_EINVAL;
     }
-    uint8_t *planes = static_cast<uint8_t *>(d_ws);  // three ow x oh planes: no upsampling at these scales
+    // three ow x oh planes: no upsampling at these scales; but of a 4:2:2 file its planes at the decoded
+    // size, whose chroma libjpeg replicates at 1 / 8 whatever its width
+    uint8_t *planes = static_cast<uint8_t *>(d_ws);
     const int e = jpegds_launch(d_in, planes, n, file_w, file_h, layout, shrink, as_stream(stream));
     if (e) return e;
+    if (layout == MIPX_YCC_422) return ycc_launch(planes, d_out, n, ow, oh, MIPX_YCC_422, as_stream(stream), shrink == 8);
     return ycc_launch(planes, d_out, n, ow, oh, MIPX_YCC_444, as_stream(stream));
 }
 

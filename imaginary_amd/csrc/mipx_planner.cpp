@@ -613,8 +613,8 @@ extern "C" int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t m
 
 // ---- planar JPEG input (MIPX_OP_YCC) ---------------------------------------------
 extern "C" size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout) {
-    if (w <= 0 || h <= 0 || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return 0;
-    const size_t cw = layout == MIPX_YCC_420 ? (static_cast<size_t>(w) + 1) / 2 : w;
+    if (w <= 0 || h <= 0 || !mipx::ycc_input_layout(layout)) return 0;
+    const size_t cw = layout != MIPX_YCC_444 ? (static_cast<size_t>(w) + 1) / 2 : w;
     const size_t ch = layout == MIPX_YCC_420 ? (static_cast<size_t>(h) + 1) / 2 : h;
     return static_cast<size_t>(w) * h + 2 * cw * ch;
 }
@@ -635,7 +635,7 @@ size_t mipx::plan_input_bytes(const mipx_plan *p) {
 }
 
 extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
-    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (!plan_header_ok(plan) || !mipx::ycc_input_layout(layout)) return MIPX_EINVAL;
     if (plan->in_bands != 3) {
         mipx::set_error("mipx_plan_set_ycc_input: the plan takes %d bands, planar YCbCr makes 3", plan->in_bands);
         return MIPX_EINVAL;
@@ -663,21 +663,24 @@ extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
 }
 
 // ---- JPEG coefficient output (MIPX_OP_JPEGC) ---------------------------------------
+// also the size of the coefficients in an input payload, so it takes the input-only 4:2:2 too
 extern "C" size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout) {
-    if (w <= 0 || h <= 0 || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return 0;
+    if (w <= 0 || h <= 0 || !mipx::ycc_input_layout(layout)) return 0;
     const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
     if (layout == MIPX_YCC_444) return 128 * 3 * ywb * yhb;
-    const size_t cwb = ((static_cast<size_t>(w) + 1) / 2 + 7) / 8, chb = ((static_cast<size_t>(h) + 1) / 2 + 7) / 8;
+    const size_t cwb = ((static_cast<size_t>(w) + 1) / 2 + 7) / 8;
+    const size_t chb = layout == MIPX_YCC_420 ? ((static_cast<size_t>(h) + 1) / 2 + 7) / 8 : yhb;
     return 128 * (ywb * yhb + 2 * cwb * chb);
 }
 
+// the output slots: of the layouts a JPEG is written in
 extern "C" size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout) {
-    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
+    const size_t coefs = mipx::ycc_output_layout(layout) ? mipx_jpegc_bytes(w, h, layout) : 0;
     return coefs ? MIPX_JPEG_SCAN_HEADER_BYTES + coefs : 0;
 }
 
 extern "C" size_t mipx_jpeg_scan_opt_bytes(int32_t w, int32_t h, int32_t layout) {
-    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
+    const size_t coefs = mipx::ycc_output_layout(layout) ? mipx_jpegc_bytes(w, h, layout) : 0;
     return coefs ? MIPX_JPEG_SCAN_OPT_HEADER_BYTES + coefs : 0;
 }
 
@@ -832,7 +835,7 @@ extern "C" size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout) {
 // op: MIPX_OP_JPEGD, or MIPX_OP_JPEGH for the same step behind the entropy decoder
 static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w, int32_t file_h,
                            const char *who, int32_t op = MIPX_OP_JPEGD) {
-    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
+    if (!plan_header_ok(plan) || !mipx::ycc_input_layout(layout)) return MIPX_EINVAL;
     if (plan->in_bands != 3) {
         mipx::set_error("%s: the plan takes %d bands, a YCbCr JPEG makes 3", who, plan->in_bands);
         return MIPX_EINVAL;

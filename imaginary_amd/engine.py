@@ -11,12 +11,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, OP_JPEGH, YCC_444, YCC_420,
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, OP_JPEGH, YCC_444, YCC_420, YCC_422,
                    JPEG_SCAN_HEADER_BYTES, JPEG_SCAN_OPT_HEADER_BYTES, JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
-           "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420",
+           "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420", "YCC_422",
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
@@ -280,7 +280,7 @@ def ycc_bytes(w: int, h: int, layout: int) -> int:
 
 def plan_set_ycc_input(plan: MipxPlan, layout: int) -> MipxPlan:
     """mipx_plan_set_ycc_input on `plan` (in place; returned for convenience): the plan then
-    takes packed JPEG planes (Y, Cb, Cr; YCC_444 or YCC_420) instead of RGB pixels."""
+    takes packed JPEG planes (Y, Cb, Cr; YCC_444, YCC_420 or YCC_422) instead of RGB pixels."""
     check(lib.mipx_plan_set_ycc_input(C.byref(plan), layout), "mipx_plan_set_ycc_input")
     return plan
 
@@ -337,7 +337,7 @@ def jpegd_bytes(w: int, h: int, layout: int) -> int:
 def plan_set_jpegd_input(plan: MipxPlan, layout: int) -> MipxPlan:
     """mipx_plan_set_jpegd_input on `plan` (in place; returned for convenience): the plan then
     takes a JPEG's quantisation tables and quantised coefficients (codec.decode_jpeg_coefs;
-    YCC_444 or YCC_420) instead of RGB pixels."""
+    YCC_444, YCC_420 or YCC_422) instead of RGB pixels."""
     check(lib.mipx_plan_set_jpegd_input(C.byref(plan), layout), "mipx_plan_set_jpegd_input")
     return plan
 
@@ -354,7 +354,7 @@ def plan_set_jpegd_input_scaled(plan: MipxPlan, layout: int, shrink: int, file_w
 
 def plan_set_jpegh_input(plan: MipxPlan, layout: int) -> MipxPlan:
     """mipx_plan_set_jpegh_input on `plan` (in place; returned for convenience): the plan then
-    takes a JPEG's tables and entropy-coded scan (codec.jpeg_huff_slot; YCC_444 or YCC_420)
+    takes a JPEG's tables and entropy-coded scan (codec.jpeg_huff_slot; YCC_444, YCC_420 or YCC_422)
     instead of RGB pixels."""
     check(lib.mipx_plan_set_jpegh_input(C.byref(plan), layout), "mipx_plan_set_jpegh_input")
     return plan

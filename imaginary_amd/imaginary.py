@@ -627,7 +627,8 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
 def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[TextMark] = None,
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
                   jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False,
-                  jpeg_huff: bool = False, jpeg_huff_restart: bool = False, jpeg_optimize: bool = False) -> Image:
+                  jpeg_huff: bool = False, jpeg_huff_restart: bool = False, jpeg_optimize: bool = False,
+                  jpeg_422: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -661,6 +662,11 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     jpeg_huff_restart: with jpeg_huff, files with a restart interval go to the engine as their scan too
     (codec.jpeg_huff_slot(buf, restart=True)), one decoder per interval; a scan whose markers are not
     the ones the interval asks for is MIPX_EDATA and goes on as jpeg_dct does.
+    jpeg_422: jpeg_dct and jpeg_huff (with jpeg_dct_shrink and jpeg_huff_restart as they are set) take
+    4:2:2 files too, what most cameras write (codec.decode_jpeg_coefs / jpeg_huff_slot with h2v1=True;
+    the engine's MIPX_YCC_422 input layout); everything those flags do is done for such a file as well,
+    and the bytes are the same either way.  `ycc` does not take 4:2:2: the stand-in decoder cannot hand
+    out its raw chroma planes.
     device_reencode: a 3-band JPEG that rotates and shrinks on load (_rotate_reencode_shrink_on_load)
     runs as one plan, the re-encode and the scaled decode as a MIPX_OP_JPEGRT step between the
     rotation and the rest: one upload, no host codec in between; the bytes are the same either way."""
@@ -701,21 +707,21 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
         px = None
         if take and jpeg_huff:
-            px = _with_scan(buf, jpeg_huff_restart,
+            px = _with_scan(buf, jpeg_huff_restart, jpeg_422,
                             lambda slot: process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq,
                                                  jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize))
         if px is None:
-            dct = codec.decode_jpeg_coefs(buf) if take else None
+            dct = _coefs(buf, jpeg_422) if take else None
             px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
                          jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
     else:
         take = (jpeg_dct or jpeg_huff) and hdr.bands == 3 and itype == "jpeg"
         px = None
         if take and jpeg_huff:
-            px = _with_scan(buf, jpeg_huff_restart,
+            px = _with_scan(buf, jpeg_huff_restart, jpeg_422,
                             lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts,
                                                  wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize))
-        dct = codec.decode_jpeg_coefs(buf) if take and px is None else None
+        dct = _coefs(buf, jpeg_422) if take and px is None else None
         planes = codec.decode_ycc(buf) if px is None and dct is None and ycc and hdr.bands == 3 else None
         if px is not None:
             pass
@@ -737,10 +743,16 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     return _encode(px, t, quality, compression)
 
 
-def _with_scan(buf: bytes, restart: bool, run):
+def _coefs(buf: bytes, h2v1: bool):
+    """codec.decode_jpeg_coefs, of 4:2:2 files too when the request opted in; the call without the
+    option stays the call it always was."""
+    return codec.decode_jpeg_coefs(buf, h2v1=True) if h2v1 else codec.decode_jpeg_coefs(buf)
+
+
+def _with_scan(buf: bytes, restart: bool, h2v1: bool, run):
     """run((slot, layout)) of the file's entropy-coded scan; None where the file has no slot
     (codec.jpeg_huff_slot) or the engine could not decode it, and the caller goes on without."""
-    slot = codec.jpeg_huff_slot(buf, restart=restart)
+    slot = codec.jpeg_huff_slot(buf, restart=restart, h2v1=True) if h2v1 else codec.jpeg_huff_slot(buf, restart=restart)
     if slot is None:
         return None
     try:

@@ -180,10 +180,14 @@ enum {
  * (libjpeg jpeg_read_raw_data, TurboJPEG tjDecompressToYUVPlanes).  One image is Y, h rows
  * of w bytes, then Cb, then Cr, ch rows of cw bytes each: no row, plane or image padding, so
  * planes and images start on any byte.  MIPX_YCC_444: cw = w, ch = h.  MIPX_YCC_420:
- * cw = ceil(w / 2), ch = ceil(h / 2).  The engine upsamples 4:2:0 chroma as libjpeg's
- * default "fancy" h2v2 upsampler does (plain replication when cw <= 2) and converts with
- * libjpeg's integer YCbCr -> RGB, bit for bit (PARITY_ASSUMPTIONS.md row 16). */
-enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
+ * cw = ceil(w / 2), ch = ceil(h / 2).  MIPX_YCC_422 (libjpeg's h2v1, what most cameras write):
+ * cw = ceil(w / 2), ch = h.  The engine upsamples 4:2:0 chroma as libjpeg's default "fancy"
+ * h2v2 upsampler does and 4:2:2 chroma as its h2v1 one does (both plain replication when
+ * cw <= 2) and converts with libjpeg's integer YCbCr -> RGB, bit for bit
+ * (PARITY_ASSUMPTIONS.md rows 16 and 25).  MIPX_YCC_422 is an input layout only: every call
+ * and plan step that writes a JPEG (MIPX_OP_JPEGC, MIPX_OP_JPEGE, MIPX_OP_JPEGRT) rejects it.
+ * The value 2 is deliberately unused: it has always been an unknown layout and stays one. */
+enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1, MIPX_YCC_422 = 3 };
 
 /* JPEG coefficient output (MIPX_OP_JPEGC): what a JPEG encoder has in front of its entropy
  * coder, so the host only Huffman-codes (libjpeg jpeg_write_coefficients).  The same two
@@ -191,8 +195,10 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * blocks only, int16 little-endian: component Y, then Cb, then Cr; each component hb x wb
  * blocks in raster order; each block 64 coefficients in natural (row-major) order, i.e.
  * libjpeg's coefficient arrays.  Y (and 4:4:4 chroma): wb = ceil(w / 8), hb = ceil(h / 8).
- * 4:2:0 chroma: wb = ceil(ceil(w / 2) / 8), hb = ceil(ceil(h / 2) / 8).  The blocks that pad a
- * partial MCU in 4:2:0 (zero AC, DC copied) are the entropy coder's and are not emitted.  The
+ * 4:2:0 chroma: wb = ceil(ceil(w / 2) / 8), hb = ceil(ceil(h / 2) / 8).  4:2:2 chroma (input
+ * only; mipx_jpegc_bytes sizes it because the input payloads are made of it):
+ * wb = ceil(ceil(w / 2) / 8), hb = ceil(h / 8).  The blocks that pad a partial MCU in 4:2:0
+ * and 4:2:2 (zero AC, DC copied) are the entropy coder's and are not emitted.  The
  * engine computes libjpeg's integer RGB -> YCbCr, its h2v2 downsample, the "islow" forward DCT
  * and the quantisation with the tables of jpeg_set_quality(quality, TRUE), bit for bit
  * (PARITY_ASSUMPTIONS.md row 17); images and both pointers start on any byte. */
@@ -215,9 +221,13 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1 };
  * jidctred.c; what jpeg_read_coefficients gives does not depend on the scale).  The output is
  * ceil(w / s) x ceil(h / s).  Y and 4:4:4 chroma blocks get the 4 x 4, 2 x 2 or 1 x 1 inverse
  * DCT; 4:2:0 chroma blocks get the next larger one (8 x 8, 4 x 4, 2 x 2), so chroma comes out at
- * the output size and nothing is upsampled; the conversion is the 4:4:4 one.  Bit for bit
- * libjpeg-turbo's on files an encoder writes, tests/jpegds_ref.py's rule elsewhere
- * (PARITY_ASSUMPTIONS.md row 19). */
+ * the output size and nothing is upsampled; the conversion is the 4:4:4 one.  4:2:2 chroma
+ * blocks get the same inverse DCT as Y (jdmaster.c enlarges a component's only when both of
+ * its sampling ratios allow it), so chroma comes out ceil(h / s) high and ceil(ceil(w / s) / 2)
+ * wide, the MIPX_YCC_422 planes of the decoded size, and is upsampled as MIPX_OP_YCC does at
+ * that size; at 1 / 8 by plain replication at every width, as libjpeg switches the fancy
+ * upsampler off there.  Bit for bit libjpeg-turbo's on files an encoder writes,
+ * tests/jpegds_ref.py's rule elsewhere (PARITY_ASSUMPTIONS.md rows 19 and 25). */
 /* JPEG round trip (MIPX_OP_JPEGRT): what re-encoding an image as a JPEG and decoding that file
  * does to its pixels, as imaginary's /pipeline does between stages and bimg does before a rotated
  * JPEG shrinks on load, without the file: exactly MIPX_OP_JPEGC's rule at (layout, quality), then
@@ -275,7 +285,8 @@ enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODA
  *         between the SOS segment and FF D9 (stuffed, restart markers included)
  *      4  uint32 restart: the file's DRI value Ri in MCUs, 0 for a file without one; then two uint32
  *         zeros.  With M the scan's MCUs (ceil(w/8) ceil(h/8) for 4:4:4, ceil(w/16) ceil(h/16) for
- *         4:2:0) and K = ceil(M / Ri): Ri = 0, or Ri <= 65535 with K = 1, is an ordinary scan
+ *         4:2:0, ceil(w/16) ceil(h/8) for 4:2:2, whose MCU is Y left, Y right, Cb, Cr) and
+ *         K = ceil(M / Ri): Ri = 0, or Ri <= 65535 with K = 1, is an ordinary scan
  *         without a marker.  Ri <= 65535 with K >= 2: the scan is K intervals with K - 1 two-byte
  *         markers between them, marker k (from 0) FF D0 + (k & 7); interval k holds the MCUs k Ri ..
  *         min((k + 1) Ri, M) - 1, starts on a byte boundary with the DC predictors 0, and is decoded

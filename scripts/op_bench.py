@@ -18,9 +18,13 @@ rocprofv3 passes see that kernel alone.
     python scripts/op_bench.py jpegh420 --file tests/golden/testdata/large.jpg --n 64   (a photograph's scan)
     python scripts/op_bench.py jpeghd420 --w 3840 --h 2160 --n 64 --q 75 --restart 8    (a restart interval of 8 MCUs)
     python scripts/op_bench.py jpeghd420 --file tests/golden/testdata/large.jpg --n 64 --restart r1   (of one MCU row)
+    python scripts/op_bench.py ycc422 --w 3840 --h 2160 --n 64              (4:2:2 planes -> RGB)
+    python scripts/op_bench.py jpegds422 --w 3840 --h 2160 --n 64 --q 75 --shrink 4
+    python scripts/op_bench.py jpeghd422 --w 3840 --h 2160 --n 64 --q 75 --restart 0   (4:2:2 scans are Pillow's: --restart)
     ops: reduce reducev reduceh shrink blur embed rot flip extract affine zoom textmark watermark ycc420 ycc444
          jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444 jpegrt420 jpegrt444
          jpege420 jpege444 jpegcs420 jpegcs444 jpegh420 jpegh444 jpeghd420 jpeghd444
+         ycc422 jpegd422 jpegds422 jpegh422 jpeghd422 (input only; jpegh422 / jpeghd422 need --restart)
 """
 import argparse
 import ctypes as C
@@ -112,19 +116,20 @@ def main():
         ob = b if b in (2, 4) else b + 1
         mask = torch.randint(0, 256, (mh * mw * 4,), dtype=torch.uint8, device=dev)
     in_img = w * h * b          # input bytes of one image
-    if a.op in ("ycc420", "ycc444"):   # packed JPEG planes in, RGB out
+    LAYOUT = {"420": 1, "444": 0, "422": 3}   # MIPX_YCC_*, by the op's last three characters
+    if a.op in ("ycc420", "ycc444", "ycc422"):   # packed JPEG planes in, RGB out
         b = ob = 3
-        layout = 1 if a.op == "ycc420" else 0
+        layout = LAYOUT[a.op[-3:]]
         in_img = lib.mipx_ycc_bytes(w, h, layout)
     out_img = ow * oh * ob      # output bytes of one image
     if a.op in ("jpegc420", "jpegc444"):   # RGB in, quantised DCT coefficients out
         b = ob = 3              # "out" names the image the step consumes; its bytes are out_img
         layout = 1 if a.op == "jpegc420" else 0
         in_img, out_img = w * h * 3, lib.mipx_jpegc_bytes(w, h, layout)
-    JPEGD = ("jpegd420", "jpegd444", "jpegds420", "jpegds444")
+    JPEGD = ("jpegd420", "jpegd444", "jpegd422", "jpegds420", "jpegds444", "jpegds422")
     if a.op in JPEGD:   # quantisation tables + quantised DCT coefficients in, RGB out
         b = ob = 3
-        layout = 1 if a.op.endswith("420") else 0
+        layout = LAYOUT[a.op[-3:]]
         in_img = lib.mipx_jpegd_bytes(w, h, layout)
         if a.op.startswith("jpegds"):   # ... at 1/shrink: the same payload, RGB at the decoded size
             ow, oh = -(-w // a.shrink), -(-h // a.shrink)
@@ -140,11 +145,13 @@ def main():
         layout = 1 if a.op.endswith("420") else 0
         in_img = w * h * 3 if a.op.startswith("jpege") else lib.mipx_jpegc_bytes(w, h, layout)
         out_img = (lib.mipx_jpeg_scan_opt_bytes if a.optimize else lib.mipx_jpeg_scan_bytes)(w, h, layout)
-    JPEGH = ("jpegh420", "jpegh444", "jpeghd420", "jpeghd444")
+    JPEGH = ("jpegh420", "jpegh444", "jpegh422", "jpeghd420", "jpeghd444", "jpeghd422")
     file_slot = None
     if a.op in JPEGH:   # one input slot per image in; RGB (jpegh*) or MIPX_OP_JPEGD's payload (jpeghd*) out
         b = ob = 3
-        layout = 1 if a.op.endswith("420") else 0
+        layout = LAYOUT[a.op[-3:]]
+        if layout == 3 and a.restart is None:
+            raise SystemExit("4:2:2 scans are Pillow's: give --restart (0 for a file without markers)")
         if a.restart is not None:
             import io
             import numpy as np
@@ -161,8 +168,8 @@ def main():
                 kw = dict(restart_marker_blocks=int(a.restart))
             ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 1 << 26)   # noise at a high quality is a long scan
             out = io.BytesIO()
-            Image.fromarray(np.ascontiguousarray(px)).save(out, "JPEG", quality=a.q, subsampling=2 if layout else 0, **kw)
-            file_slot, layout = codec.jpeg_huff_slot(out.getvalue(), restart=True)
+            Image.fromarray(np.ascontiguousarray(px)).save(out, "JPEG", quality=a.q, subsampling={0: 0, 1: 2, 3: 1}[layout], **kw)
+            file_slot, layout = codec.jpeg_huff_slot(out.getvalue(), restart=True, h2v1=layout == 3)
             w, h = px.shape[1], px.shape[0]
             ow, oh = w, h
         elif a.file:
@@ -231,8 +238,20 @@ def main():
         coefs = torch.empty((n * (in_img - 384),), dtype=torch.uint8, device=dev)
         assert coefs.numel() == n * lib.mipx_jpegc_bytes(w, h, layout)
         torch.cuda.synchronize(dev)
-        assert lib.mipx_op_rgb_to_jpegc(px.data_ptr(), coefs.data_ptr(), n, w, h, layout, a.q, None) == 0
-        check(lib.mipx_device_sync())
+        if layout == 3:
+            # the engine writes no 4:2:2: the 4:4:4 coefficients of the same pixels, Y whole and of each chroma
+            # component the left ceil(ceil(w / 2) / 8) block columns (an encoder's blocks of noise all the same)
+            ywb, yhb, cwb = (w + 7) // 8, (h + 7) // 8, ((w + 1) // 2 + 7) // 8
+            full = torch.empty((n, 3, yhb, ywb, 128), dtype=torch.uint8, device=dev)
+            assert lib.mipx_op_rgb_to_jpegc(px.data_ptr(), full.data_ptr(), n, w, h, 0, a.q, None) == 0
+            check(lib.mipx_device_sync())
+            cv = coefs.view(n, in_img - 384)
+            cv[:, :yhb * ywb * 128] = full[:, 0].reshape(n, -1)
+            cv[:, yhb * ywb * 128:] = full[:, 1:, :, :cwb].reshape(n, -1)
+            del full
+        else:
+            assert lib.mipx_op_rgb_to_jpegc(px.data_ptr(), coefs.data_ptr(), n, w, h, layout, a.q, None) == 0
+            check(lib.mipx_device_sync())
         xv = x.view(n, in_img)
         xv[:, 384:] = coefs.view(n, in_img - 384)
         xv[:, :384] = torch.from_numpy(head).to(dev)
@@ -270,13 +289,13 @@ def main():
             return lib.mipx_op_text_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, margin, a.opacity, colour, sp)
         if a.op == "watermark":
             return lib.mipx_op_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, 4, 100, 100, a.opacity, sp)
-        if a.op in ("ycc420", "ycc444"):
+        if a.op in ("ycc420", "ycc444", "ycc422"):
             return lib.mipx_op_ycc_to_rgb(X, Y, n, w, h, layout, sp)
         if a.op in ("jpegc420", "jpegc444"):
             return lib.mipx_op_rgb_to_jpegc(X, Y, n, w, h, layout, a.q, sp)
-        if a.op in ("jpegd420", "jpegd444"):
+        if a.op in ("jpegd420", "jpegd444", "jpegd422"):
             return lib.mipx_op_jpegd_to_rgb(X, Y, n, w, h, layout, WS, WSB, sp)
-        if a.op in ("jpegds420", "jpegds444"):
+        if a.op in ("jpegds420", "jpegds444", "jpegds422"):
             return lib.mipx_op_jpegd_to_rgb_scaled(X, Y, n, w, h, layout, a.shrink, WS, WSB, sp)
         if a.op in ("jpegrt420", "jpegrt444"):
             return lib.mipx_op_jpeg_roundtrip(X, Y, n, w, h, layout, a.q, a.shrink, WS, WSB, sp)
@@ -292,9 +311,9 @@ def main():
             if a.optimize:
                 return lib.mipx_op_jpegc_to_scan_optimized(X, Y, n, w, h, layout, WS, sp)
             return lib.mipx_op_jpegc_to_scan(X, Y, n, w, h, layout, WS, sp)
-        if a.op in ("jpegh420", "jpegh444"):
+        if a.op in ("jpegh420", "jpegh444", "jpegh422"):
             return lib.mipx_op_jpegh_to_rgb(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
-        if a.op in ("jpeghd420", "jpeghd444"):
+        if a.op in ("jpeghd420", "jpeghd444", "jpeghd422"):
             return lib.mipx_op_jpegh_to_jpegd(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
         raise SystemExit(a.op)
 
