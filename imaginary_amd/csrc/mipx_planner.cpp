@@ -95,7 +95,9 @@ struct ColourTables {
         }
         for (int i = 0; i < kQuantElements; ++i) {
             const float y = static_cast<double>(i) / kQuantElements;
-            cbrt[i] = y < 0.008856 ? 7.787 * y + (16.0 / 116.0) : std::cbrt(y);
+            // XYZ2Lab.c is C: cbrt() there is the double function, rounded to float once.
+            // std::cbrt(float) would be cbrtf, one ulp off in 11,553 of the entries.
+            cbrt[i] = y < 0.008856 ? 7.787 * y + (16.0 / 116.0) : std::cbrt(static_cast<double>(y));
         }
     }
 };

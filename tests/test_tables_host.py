@@ -3,7 +3,9 @@ uploaded before they were split from the runtime: tests/c/tables_host.cpp runs e
 builder over a fixed parameter list (no HIP call, no GPU) and prints one hash per table;
 tests/golden/tables_host.txt holds those hashes as computed by the device_* functions of
 the commit before the split, compiled for the host with the four HIP calls they make
-replaced by malloc / memcpy / free."""
+replaced by malloc / memcpy / free.  One line has changed since: colour_tables, when the
+cube-root look-up went from cbrtf to the double cbrt that libvips calls
+(tests/test_smartcrop_cpu.py compares that table with the formula entry by entry)."""
 import os
 import subprocess
 
