@@ -1,5 +1,6 @@
 // jpeg_dct.h — the device functions the JPEG kernels share (k_jpegc.hip, k_jpegd.hip,
-// k_jpegrt.hip): libjpeg's colour conversion and downsample into the blocks' LDS image, its
+// k_jpegrt.hip): libjpeg's colour conversion and downsample into the blocks' LDS image, the
+// place of each of a strip's blocks in its component's grid, its
 // forward DCT and quantisation (jfdct), its dequantisation and inverse DCTs (jidct).  One copy
 // of each pass; the rules themselves are stated at the top of k_jpegc.hip and k_jpegd.hip.
 #pragma once
@@ -118,6 +119,24 @@ __device__ __forceinline__ void strip_samples(int16_t *blocks, const u8 *in, uin
         *reinterpret_cast<uint32_t *>(c + 8 * kBlockPitch) =
             pack16(((sr[0] + 1) >> 2) - 128, ((sr[1] + 2) >> 2) - 128);
     }
+}
+
+// Block `blk` of that strip: its component (0: Y, 1: Cb, 2: Cr) and its column and row in that
+// component's block grid; false for a block outside the real ones (ywb, yhb: real Y blocks across
+// and down; cwb: real chroma blocks across).  k_jpegc.hip's block_offset keeps a copy of this map.
+template <int LAYOUT>
+__device__ __forceinline__ bool strip_block(uint32_t ywb, uint32_t yhb, uint32_t cwb, uint32_t sx, uint32_t sy,
+                                            uint32_t blk, uint32_t *comp, uint32_t *bx, uint32_t *by) {
+    if (LAYOUT == MIPX_YCC_444) {
+        *comp = blk >> 4, *bx = sx * 16u + (blk & 15u), *by = sy;
+        return *bx < ywb;
+    }
+    if (blk < 32u) {
+        *comp = 0u, *bx = sx * 16u + (blk & 15u), *by = sy * 2u + (blk >> 4);
+        return *bx < ywb && *by < yhb;
+    }
+    *comp = blk < 40u ? 1u : 2u, *bx = sx * 8u + (blk & 7u), *by = sy;
+    return *bx < cwb;
 }
 
 // One 8-point pass of jfdctint.c in place.  FIRST: the rows pass (outputs scaled up by

@@ -139,25 +139,22 @@ __global__ void __launch_bounds__(256) k_jpegd(const JpegdArgs a) {
 // The caller has checked that an image's payload and its RGB are below 2^32 bytes, so every
 // byte offset inside an image fits 32 bits.
 int jpegd_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, hipStream_t st) {
-    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
+    const JpegGeom g(w, h, layout);
     JpegdArgs a;
     a.in = d_in, a.out = d_planes;
-    a.in_img = static_cast<long long>(mipx_jpegd_bytes(w, h, layout));
-    a.out_img = static_cast<long long>(mipx_ycc_bytes(w, h, layout));
-    a.pw[0] = w, a.ph[0] = h;
-    a.pw[1] = sub || h2v1 ? (static_cast<uint32_t>(w) + 1u) / 2u : w;
-    a.ph[1] = sub ? (static_cast<uint32_t>(h) + 1u) / 2u : h;
+    a.in_img = static_cast<long long>(MIPX_JPEGD_HEADER_BYTES + g.coef_bytes);
+    a.out_img = static_cast<long long>(g.plane_bytes);
     long long total = 0;
     for (int c = 0; c < 2; ++c) {
-        a.wb[c] = (a.pw[c] + 7u) / 8u, a.hb[c] = (a.ph[c] + 7u) / 8u;
+        a.pw[c] = static_cast<uint32_t>(g.of(c).w), a.ph[c] = static_cast<uint32_t>(g.of(c).h);
+        a.wb[c] = static_cast<uint32_t>(g.of(c).wb), a.hb[c] = static_cast<uint32_t>(g.of(c).hb);
         a.runs[c] = (a.wb[c] + kRun - 1u) / kRun;
         a.groups[c] = a.runs[c] * a.hb[c];
         total += static_cast<long long>(a.runs[c]) * a.hb[c] * (c ? 2 : 1);
     }
     if (!grid_ok(total)) return MIPX_EUNSUPPORTED;
-    a.coef_off[0] = 0u, a.plane_off[0] = 0u;
-    a.coef_off[1] = a.wb[0] * a.hb[0] * 128u, a.plane_off[1] = a.pw[0] * a.ph[0];
-    a.coef_off[2] = a.coef_off[1] + a.wb[1] * a.hb[1] * 128u, a.plane_off[2] = a.plane_off[1] + a.pw[1] * a.ph[1];
+    for (int c = 0; c < 3; ++c)
+        a.coef_off[c] = static_cast<uint32_t>(g.coef_off[c]), a.plane_off[c] = static_cast<uint32_t>(g.plane_off[c]);
     hipLaunchKernelGGL(k_jpegd, dim3(static_cast<unsigned>(total), n), dim3(256), 0, st, a);
     return launch_check("k_jpegd");
 }
@@ -351,21 +348,18 @@ __global__ void __launch_bounds__(256) k_jpegds(const JpegdsArgs a) {
 // w x h is the file's size.  The caller has checked that the payload and the RGB at the output
 // size are below 2^32 bytes, and that shrink is 2, 4 or 8.
 int jpegds_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, int shrink, hipStream_t st) {
-    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
-    const uint32_t s = static_cast<uint32_t>(shrink);
+    const JpegGeom g(w, h, layout);
+    const JpegPlanes p = g.planes(shrink);  // below full size both planes are ceil(h / shrink) high
     JpegdsArgs a;
     a.in = d_in, a.out = d_planes;
-    a.in_img = static_cast<long long>(mipx_jpegd_bytes(w, h, layout));
-    a.pw[0] = (static_cast<uint32_t>(w) + s - 1u) / s, a.ph = (static_cast<uint32_t>(h) + s - 1u) / s;
-    a.pw[1] = h2v1 ? (a.pw[0] + 1u) / 2u : a.pw[0];
-    a.plane_off[0] = 0u, a.plane_off[1] = a.pw[0] * a.ph, a.plane_off[2] = a.plane_off[1] + a.pw[1] * a.ph;
-    a.out_img = static_cast<long long>(a.plane_off[2]) + a.pw[1] * a.ph;
-    const uint32_t cw[2] = {static_cast<uint32_t>(w), sub || h2v1 ? (static_cast<uint32_t>(w) + 1u) / 2u : w};
-    const uint32_t ch[2] = {static_cast<uint32_t>(h), sub ? (static_cast<uint32_t>(h) + 1u) / 2u : h};
-    a.nidct[0] = 8u / s, a.nidct[1] = sub ? 16u / s : 8u / s;
+    a.in_img = static_cast<long long>(MIPX_JPEGD_HEADER_BYTES + g.coef_bytes);
+    a.out_img = static_cast<long long>(p.bytes);
+    a.ph = static_cast<uint32_t>(p.h[0]);
+    for (int c = 0; c < 3; ++c) a.plane_off[c] = static_cast<uint32_t>(p.off[c]);
     long long total = 0;
     for (int c = 0; c < 2; ++c) {
-        a.wb[c] = (cw[c] + 7u) / 8u, a.hb[c] = (ch[c] + 7u) / 8u;
+        a.pw[c] = static_cast<uint32_t>(p.w[c]), a.nidct[c] = p.n[c];
+        a.wb[c] = static_cast<uint32_t>(g.of(c).wb), a.hb[c] = static_cast<uint32_t>(g.of(c).hb);
         if (a.nidct[c] == 1u) {  // linear over the block grid, which is the plane
             if (a.wb[c] != a.pw[c] || a.hb[c] != a.ph) return MIPX_EINVAL;
             const uint32_t per = 256u * kDcPerLane;
@@ -379,9 +373,7 @@ int jpegds_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout,
         total += static_cast<long long>(a.groups[c]) * (c ? 2 : 1);
     }
     if (!grid_ok(total)) return MIPX_EUNSUPPORTED;
-    a.coef_off[0] = 0u;
-    a.coef_off[1] = a.wb[0] * a.hb[0] * 128u;
-    a.coef_off[2] = a.coef_off[1] + a.wb[1] * a.hb[1] * 128u;
+    for (int c = 0; c < 3; ++c) a.coef_off[c] = static_cast<uint32_t>(g.coef_off[c]);
     hipLaunchKernelGGL(k_jpegds, dim3(static_cast<unsigned>(total), n), dim3(256), 0, st, a);
     return launch_check("k_jpegds");
 }

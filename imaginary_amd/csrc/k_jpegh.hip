@@ -51,11 +51,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "jpeg_scan.h"
 
 namespace mipx {
 namespace {
 
 using namespace dev;
+using namespace jscan;
 
 constexpr uint32_t kLanes = kJpeghSeq;       // threads of every kernel here
 constexpr uint32_t kSubBits = 8u * kJpeghSub;
@@ -70,9 +72,6 @@ static_assert(kPending != MIPX_JPEGH_OK && kPending != MIPX_JPEGH_UNSYNCED && kP
 // them, and one more so that the lanes of a wave, each at its own bit, read 64 different banks
 constexpr uint32_t kStagePitch = kJpeghSub / 4u + 3u;
 static_assert(kJpeghSub % 4 == 0 && (kStagePitch & 1u) == 1u, "an odd pitch spreads the lanes over the banks");
-// blocks of an MCU: Y Cb Cr; Y00 Y01 Y10 Y11 Cb Cr; 4:2:2's Y0 Y1 Cb Cr
-template <int LAYOUT>
-constexpr uint32_t per_mcu() { return LAYOUT == MIPX_YCC_444 ? 3u : LAYOUT == MIPX_YCC_422 ? 4u : 6u; }
 constexpr uint32_t kTablesOff = 416, kTableBytes = 272, kSelOff = 400, kQuantOff = 16;
 static_assert(kLanes == 256, "block_scan sums four waves");
 
@@ -108,30 +107,6 @@ struct JpeghArgs {
     uint32_t ywb, yhb, mw;
     uint32_t cb_off, cr_off;       // byte offsets of Cb and Cr in the payload's coefficients
 };
-
-// Exclusive prefix of v over the workgroup's 256 lanes; *total = the sum.  wsum: 4 words of LDS.
-template <class T>
-__device__ __forceinline__ T block_scan(T v, T *wsum, T *total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T t = __shfl_up(inc, d);
-        if (lane >= static_cast<uint32_t>(d)) inc += t;
-    }
-    if (lane == 63u) wsum[wave] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kLanes / 64u; ++i) {
-        const T s = wsum[i];
-        base += i < wave ? s : T(0);
-        tot += s;
-    }
-    __syncthreads();  // wsum is free again
-    *total = tot;
-    return base + inc - v;
-}
 
 __device__ __forceinline__ uint32_t load_u32(const u8 *p) {
     uint32_t v;
@@ -565,36 +540,11 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_place(const JpeghArgs a) {
 // Byte offset in the payload's coefficients of block `cur` of the scan; kNone for a dummy block.
 template <int LAYOUT>
 __device__ __forceinline__ uint32_t block_dst(const JpeghArgs &a, uint32_t cur, uint32_t *comp) {
-    if (LAYOUT == MIPX_YCC_444) {
-        const uint32_t m = cur / 3u, c = cur - 3u * m;
-        *comp = c;
-        return (c == 0u ? 0u : c == 1u ? a.cb_off : a.cr_off) + m * 128u;
-    }
-    if (LAYOUT == MIPX_YCC_422) {  // the chroma grid is the MCU grid; Y block j is the MCU's column j
-        const uint32_t m = cur / 4u, j = cur - 4u * m;
-        if (j >= 2u) {
-            *comp = j - 1u;
-            return (j == 2u ? a.cb_off : a.cr_off) + m * 128u;
-        }
-        *comp = 0u;
-        const uint32_t my = m / a.mw, mx = m - my * a.mw;
-        const uint32_t bx = 2u * mx + j;
-        return bx < a.ywb ? (my * a.ywb + bx) * 128u : kNone;
-    }
-    const uint32_t m = cur / 6u, j = cur - 6u * m;
-    if (j >= 4u) {
-        *comp = j - 3u;
-        return (j == 4u ? a.cb_off : a.cr_off) + m * 128u;
-    }
-    *comp = 0u;
-    const uint32_t my = m / a.mw, mx = m - my * a.mw;
-    const uint32_t by = 2u * my + (j >> 1), bx = 2u * mx + (j & 1u);
-    return by < a.yhb && bx < a.ywb ? (by * a.ywb + bx) * 128u : kNone;
+    const ScanBlock b = scan_block<LAYOUT>(cur, a.mw);
+    *comp = b.comp;
+    if (!b.placed) return (b.comp == 0u ? 0u : b.comp == 1u ? a.cb_off : a.cr_off) + b.m * 128u;
+    return b.by < a.yhb && b.bx < a.ywb ? (b.by * a.ywb + b.bx) * 128u : kNone;
 }
-
-__constant__ uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 template <int LAYOUT>
 __global__ void __launch_bounds__(kLanes) k_jpegh_write(const JpeghArgs a) {
@@ -633,7 +583,7 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_write(const JpeghArgs a) {
                 dcdiff[cur] = r.coef;
             } else if (dst != kNone && r.coef != 0) {
                 const int16_t c = static_cast<int16_t>(r.coef);  // 15 bits and a sign at most
-                __builtin_memcpy(coefs + dst + 2u * kNatural[r.k], &c, 2);  // dst + 128 <= cap
+                __builtin_memcpy(coefs + dst + 2u * kZigzag[r.k], &c, 2);  // dst + 128 <= cap
             }
         }
         if (r.block_end) {
@@ -647,23 +597,12 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_write(const JpeghArgs a) {
 // ---- the DC prediction chain ----------------------------------------------------------------
 
 template <int LAYOUT>
-__device__ __forceinline__ uint32_t comp_of(uint32_t cur) {
-    if (LAYOUT == MIPX_YCC_444) return cur % 3u;
-    if (LAYOUT == MIPX_YCC_422) {
-        const uint32_t j = cur % 4u;
-        return j < 2u ? 0u : j - 1u;
-    }
-    const uint32_t j = cur % 6u;
-    return j < 4u ? 0u : j - 3u;
-}
-
-template <int LAYOUT>
 __global__ void __launch_bounds__(kLanes) k_jpegh_dcsum(const JpeghArgs a) {
     __shared__ int wsum[kLanes / 64];
     const uint32_t img = blockIdx.y, tile = blockIdx.x, cur = tile * kLanes + threadIdx.x;
     if (a.status[img] != MIPX_JPEGH_OK) return;
     const int d = cur < a.blocks ? a.dcdiff[static_cast<size_t>(img) * a.wblocks + cur] : 0;
-    const uint32_t comp = comp_of<LAYOUT>(cur);
+    const uint32_t comp = scan_block<LAYOUT>(cur, 1u).comp;
 #pragma unroll
     for (uint32_t c = 0; c < 3u; ++c) {
         int total;  // 256 differences of 15 bits and a sign
@@ -846,7 +785,7 @@ __global__ void __launch_bounds__(kLanes) k_jpegr_decode(const JpeghArgs a) {
                 }
             } else if (dst != kNone && r.coef != 0) {
                 const int16_t c = static_cast<int16_t>(r.coef);
-                __builtin_memcpy(coefs + dst + 2u * kNatural[r.k], &c, 2);  // dst + 128 <= cap
+                __builtin_memcpy(coefs + dst + 2u * kZigzag[r.k], &c, 2);  // dst + 128 <= cap
             }
         }
         if (r.block_end) {
@@ -862,7 +801,7 @@ __global__ void __launch_bounds__(kLanes) k_jpegr_decode(const JpeghArgs a) {
 int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, int w, int h, int layout, u8 *work,
                  hipStream_t st) {
     const JpeghWork W(n, w, h);
-    const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
+    const JpegGeom g(w, h, layout);
     JpeghArgs a;
     a.slots = d_slots, a.payloads = d_payloads, a.status = d_status;
     a.info = reinterpret_cast<JpeghInfo *>(work + W.info);
@@ -878,27 +817,21 @@ int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, i
     a.dc_sums = reinterpret_cast<int *>(work + W.dc_sums);
     a.dc_offs = reinterpret_cast<long long *>(work + W.dc_offs);
     a.n = static_cast<uint32_t>(n);
-    a.cap = static_cast<uint32_t>(mipx_jpegc_bytes(w, h, layout));
+    // the grids of this image: by its own capacity, inside the workspace's strides
+    const uint64_t chunks = (g.coef_bytes + kChunk - 1) / kChunk;
+    const uint64_t seqs = (g.coef_bytes + kJpeghSub * kLanes - 1) / (kJpeghSub * kLanes);
+    const uint64_t tiles = (g.blocks + kLanes - 1) / kLanes, mcus = g.mw * g.mh;
+    if (g.coef_bytes > W.cap || !jpeg_scan_fits_decoder(g) || g.blocks > W.blocks || chunks > W.chunks ||
+        seqs > W.seqs || tiles > W.tiles || !grid_ok(chunks) || !grid_ok(tiles) ||
+        mcus > W.seqs * kLanes)  // the interval table's room in `counts`
+        return MIPX_EUNSUPPORTED;
+    a.cap = static_cast<uint32_t>(g.coef_bytes);
     a.sstride = static_cast<uint32_t>(W.sstride);
     a.chunks = static_cast<uint32_t>(W.chunks), a.seqs = static_cast<uint32_t>(W.seqs), a.tiles = static_cast<uint32_t>(W.tiles);
     a.wblocks = static_cast<uint32_t>(W.blocks);
-    a.ywb = (static_cast<uint32_t>(w) + 7u) / 8u, a.yhb = (static_cast<uint32_t>(h) + 7u) / 8u;
-    const uint32_t cwb = sub || h2v1 ? ((static_cast<uint32_t>(w) + 1u) / 2u + 7u) / 8u : a.ywb;
-    const uint32_t chb = sub ? ((static_cast<uint32_t>(h) + 1u) / 2u + 7u) / 8u : a.yhb;
-    a.mw = cwb;
-    a.cb_off = a.ywb * a.yhb * 128u;
-    a.cr_off = a.cb_off + cwb * chb * 128u;
-    const unsigned long long blocks = static_cast<unsigned long long>(cwb) * chb * (sub ? 6u : h2v1 ? 4u : 3u);
-    a.blocks = static_cast<uint32_t>(blocks);
-    a.mcus = cwb * chb;
-    // the grids of this image: by its own capacity, inside the workspace's strides
-    const uint32_t chunks = (a.cap + kChunk - 1u) / kChunk;
-    const uint32_t seqs = (a.cap + kJpeghSub * kLanes - 1u) / (kJpeghSub * kLanes);
-    const uint32_t tiles = static_cast<uint32_t>((blocks + kLanes - 1u) / kLanes);
-    if (a.cap > W.cap || a.cap >= (1u << 29) || blocks > W.blocks || chunks > W.chunks || seqs > W.seqs ||
-        tiles > W.tiles || !grid_ok(chunks) || !grid_ok(tiles) ||
-        a.mcus > W.seqs * kLanes)  // the interval table's room in `counts`
-        return MIPX_EUNSUPPORTED;
+    a.ywb = static_cast<uint32_t>(g.y.wb), a.yhb = static_cast<uint32_t>(g.y.hb), a.mw = static_cast<uint32_t>(g.mw);
+    a.cb_off = static_cast<uint32_t>(g.coef_off[1]), a.cr_off = static_cast<uint32_t>(g.coef_off[2]);
+    a.blocks = static_cast<uint32_t>(g.blocks), a.mcus = static_cast<uint32_t>(mcus);
     MIPX_HIP(hipMemsetAsync(d_status, 0, static_cast<size_t>(n) * 4, st));
     MIPX_HIP(hipMemsetAsync(work + W.info, 0, static_cast<size_t>(n) * sizeof(JpeghInfo), st));
     MIPX_HIP(hipMemsetAsync(d_payloads, 0, static_cast<size_t>(n) * (MIPX_JPEGD_HEADER_BYTES + static_cast<size_t>(a.cap)), st));
@@ -913,33 +846,23 @@ int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, i
     // the restart path: images with a restart interval finish here, every other leaves at once
     hipLaunchKernelGGL(k_jpegr_index, by_index, threads, 0, st, a);
     if ((e = launch_check("k_jpegr_index"))) return e;
-    if (sub) hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_420>, by_interval, threads, 0, st, a);
-    else if (h2v1) hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_422>, by_interval, threads, 0, st, a);
-    else hipLaunchKernelGGL(k_jpegr_decode<MIPX_YCC_444>, by_interval, threads, 0, st, a);
+    with_input_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_jpegr_decode<L.value>, by_interval, threads, 0, st, a); });
     if ((e = launch_check("k_jpegr_decode"))) return e;
     hipLaunchKernelGGL(k_jpegh_unstuff, by_chunk, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_unstuff"))) return e;
     for (uint32_t round = 0; round <= kJpeghRounds; ++round) {
-        if (sub) hipLaunchKernelGGL(k_jpegh_sync<MIPX_YCC_420>, by_seq, threads, 0, st, a, round);
-        else if (h2v1) hipLaunchKernelGGL(k_jpegh_sync<MIPX_YCC_422>, by_seq, threads, 0, st, a, round);
-        else hipLaunchKernelGGL(k_jpegh_sync<MIPX_YCC_444>, by_seq, threads, 0, st, a, round);
+        with_input_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_jpegh_sync<L.value>, by_seq, threads, 0, st, a, round); });
         if ((e = launch_check("k_jpegh_sync"))) return e;
     }
     hipLaunchKernelGGL(k_jpegh_place, by_image, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_place"))) return e;
-    if (sub) hipLaunchKernelGGL(k_jpegh_write<MIPX_YCC_420>, by_seq, threads, 0, st, a);
-    else if (h2v1) hipLaunchKernelGGL(k_jpegh_write<MIPX_YCC_422>, by_seq, threads, 0, st, a);
-    else hipLaunchKernelGGL(k_jpegh_write<MIPX_YCC_444>, by_seq, threads, 0, st, a);
+    with_input_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_jpegh_write<L.value>, by_seq, threads, 0, st, a); });
     if ((e = launch_check("k_jpegh_write"))) return e;
-    if (sub) hipLaunchKernelGGL(k_jpegh_dcsum<MIPX_YCC_420>, by_tile, threads, 0, st, a);
-    else if (h2v1) hipLaunchKernelGGL(k_jpegh_dcsum<MIPX_YCC_422>, by_tile, threads, 0, st, a);
-    else hipLaunchKernelGGL(k_jpegh_dcsum<MIPX_YCC_444>, by_tile, threads, 0, st, a);
+    with_input_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_jpegh_dcsum<L.value>, by_tile, threads, 0, st, a); });
     if ((e = launch_check("k_jpegh_dcsum"))) return e;
     hipLaunchKernelGGL(k_jpegh_dcscan, by_image, threads, 0, st, a);
     if ((e = launch_check("k_jpegh_dcscan"))) return e;
-    if (sub) hipLaunchKernelGGL(k_jpegh_dcwrite<MIPX_YCC_420>, by_tile, threads, 0, st, a);
-    else if (h2v1) hipLaunchKernelGGL(k_jpegh_dcwrite<MIPX_YCC_422>, by_tile, threads, 0, st, a);
-    else hipLaunchKernelGGL(k_jpegh_dcwrite<MIPX_YCC_444>, by_tile, threads, 0, st, a);
+    with_input_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_jpegh_dcwrite<L.value>, by_tile, threads, 0, st, a); });
     return launch_check("k_jpegh_dcwrite");
 }
 

@@ -48,23 +48,6 @@ struct JpegrtArgs {
     uint32_t gx;                // strips across one image
 };
 
-// Block `blk` of strip (sx, sy): its component and its place in that component's block grid;
-// false for a block outside the real ones
-template <int LAYOUT>
-__device__ __forceinline__ bool block_place(const JpegrtArgs &a, uint32_t sx, uint32_t sy, uint32_t blk,
-                                            uint32_t *comp, uint32_t *bx, uint32_t *by) {
-    if (LAYOUT == MIPX_YCC_444) {
-        *comp = blk >> 4, *bx = sx * 16u + (blk & 15u), *by = sy;
-        return *bx < a.ywb;
-    }
-    if (blk < 32u) {
-        *comp = 0u, *bx = sx * 16u + (blk & 15u), *by = sy * 2u + (blk >> 4);
-        return *bx < a.ywb && *by < a.yhb;
-    }
-    *comp = blk < 40u ? 1u : 2u, *bx = sx * 8u + (blk & 7u), *by = sy;
-    return *bx < a.cwb;
-}
-
 // S: the scale 1, 2, 4 or 8
 template <int LAYOUT, int S>
 __global__ void __launch_bounds__(256) k_jpegrt(const JpegrtArgs a) {
@@ -92,7 +75,7 @@ __global__ void __launch_bounds__(256) k_jpegrt(const JpegrtArgs a) {
         uint32_t bx, by;
         real[i] = false, comp[i] = 0u, line[i] = t & 7u;
         blk[i] = blocks + (t >> 3) * kBlockPitch;
-        if (t < 8u * kBlocks) real[i] = block_place<LAYOUT>(a, sx, sy, t >> 3, &comp[i], &bx, &by);
+        if (t < 8u * kBlocks) real[i] = jfdct::strip_block<LAYOUT>(a.ywb, a.yhb, a.cwb, sx, sy, t >> 3, &comp[i], &bx, &by);
     }
 
     // ---- B: the rows pass of the forward DCT
@@ -136,7 +119,7 @@ __global__ void __launch_bounds__(256) k_jpegrt(const JpegrtArgs a) {
         if (t >= 8u * kBlocks) continue;
         const uint32_t b = (t >> 7) * 16u + (t & 15u), r = (t >> 4) & 7u;
         uint32_t c, bx, by;
-        if (!block_place<LAYOUT>(a, sx, sy, b, &c, &bx, &by)) continue;
+        if (!jfdct::strip_block<LAYOUT>(a.ywb, a.yhb, a.cwb, sx, sy, b, &c, &bx, &by)) continue;
         const auto pass2 = [&](auto n) {
             constexpr int N = decltype(n)::value;
             const uint32_t pw = c ? a.pw[1] : a.pw[0], ph = c ? a.ph[1] : a.ph[0];
@@ -182,8 +165,8 @@ void launch(int shrink, dim3 grid, hipStream_t st, const JpegrtArgs &a) {
 // every byte offset inside an image fits 32 bits), and that shrink is 1, 2, 4 or 8.
 int jpegrt_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, int quality, int shrink,
                   hipStream_t st) {
-    const bool sub = layout == MIPX_YCC_420;
-    const uint32_t s = static_cast<uint32_t>(shrink);
+    const JpegGeom g(w, h, layout);
+    const JpegPlanes p = g.planes(shrink);  // 4:2:0 at full size is the only case whose chroma planes are smaller than Y's
     JpegrtArgs a;
     a.in = d_in, a.out = d_planes;
     a.recips = device_jpegc_recips(quality);
@@ -193,25 +176,16 @@ int jpegrt_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout,
     }
     a.in_img = static_cast<long long>(w) * h * 3;
     a.w = w, a.h = h;
-    a.ywb = (static_cast<uint32_t>(w) + 7u) / 8u, a.yhb = (static_cast<uint32_t>(h) + 7u) / 8u;
-    a.ch = (static_cast<uint32_t>(h) + 1u) / 2u;
-    a.cwb = sub ? ((static_cast<uint32_t>(w) + 1u) / 2u + 7u) / 8u : a.ywb;
-    const uint32_t chb = sub ? (a.ch + 7u) / 8u : a.yhb;
-    a.pw[0] = (static_cast<uint32_t>(w) + s - 1u) / s, a.ph[0] = (static_cast<uint32_t>(h) + s - 1u) / s;
-    const bool half = sub && shrink == 1;  // the only case whose chroma planes are smaller than Y's
-    a.pw[1] = half ? (static_cast<uint32_t>(w) + 1u) / 2u : a.pw[0];
-    a.ph[1] = half ? a.ch : a.ph[0];
-    a.plane_off[0] = 0u;
-    a.plane_off[1] = a.pw[0] * a.ph[0];
-    a.plane_off[2] = a.plane_off[1] + a.pw[1] * a.ph[1];
-    a.out_img = static_cast<long long>(a.plane_off[2]) + a.pw[1] * a.ph[1];
-    const long long gx = (static_cast<long long>(w) + 127) / 128;
-    const long long gy = sub ? chb : a.yhb;
+    a.ywb = static_cast<uint32_t>(g.y.wb), a.yhb = static_cast<uint32_t>(g.y.hb);
+    a.cwb = static_cast<uint32_t>(g.c.wb), a.ch = static_cast<uint32_t>(g.c.h);
+    for (int c = 0; c < 2; ++c) a.pw[c] = static_cast<uint32_t>(p.w[c]), a.ph[c] = static_cast<uint32_t>(p.h[c]);
+    for (int c = 0; c < 3; ++c) a.plane_off[c] = static_cast<uint32_t>(p.off[c]);
+    a.out_img = static_cast<long long>(p.bytes);
+    const long long gx = (static_cast<long long>(w) + 127) / 128, gy = static_cast<long long>(g.mh);  // a strip is a row of MCUs
     if (!grid_ok(gx * gy)) return MIPX_EUNSUPPORTED;
     a.gx = static_cast<uint32_t>(gx);
     const dim3 grid(static_cast<unsigned>(gx * gy), n);
-    if (sub) launch<MIPX_YCC_420>(shrink, grid, st, a);
-    else launch<MIPX_YCC_444>(shrink, grid, st, a);
+    with_output_layout(layout, [&](auto L) { launch<L.value>(shrink, grid, st, a); });
     return launch_check("k_jpegrt");
 }
 

@@ -318,13 +318,14 @@ int ycc_launch(const u8 *d_in, u8 *d_out, int n, int w, int h, int layout, hipSt
         return MIPX_EUNSUPPORTED;
     }
     const bool sub = layout == MIPX_YCC_420, h2v1 = layout == MIPX_YCC_422;
+    const JpegGeom g(w, h, layout);
     YccArgs a;
     a.in = d_in, a.out = d_out;
     a.w = w, a.h = h;
-    a.cw = sub || h2v1 ? (w + 1) / 2 : w, a.ch = sub ? (h + 1) / 2 : h;
+    a.cw = static_cast<uint32_t>(g.c.w), a.ch = static_cast<uint32_t>(g.c.h);
     a.npix = static_cast<uint32_t>(npix);
     a.cpix = a.cw * a.ch;
-    a.in_img = npix + 2LL * a.cpix, a.out_img = npix * 3;
+    a.in_img = static_cast<long long>(g.plane_bytes), a.out_img = npix * 3;
     a.rep = (sub && a.cw <= 2) || (h2v1 && (a.cw <= 2 || replicate));
     a.gx = 1;
     if (h2v1) {

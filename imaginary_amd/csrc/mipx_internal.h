@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "jpeg_geom.h"    // the JPEG layouts: sizes, offsets, predicates, limits (no HIP)
 #include "mipx.h"
 #include "mipx_tables.h"  // the libvips table maths, table layouts and host builders (no HIP)
 
@@ -223,8 +224,8 @@ int jpegrt_launch(const uint8_t *in, uint8_t *planes, int n, int w, int h, int l
 int jpege_launch(const uint8_t *coefs, uint8_t *out, int n, int w, int h, int layout, bool optimise, uint8_t *work,
                  hipStream_t st, unsigned long long *d_dir = nullptr);
 // The coder's workspace, sized without the layout (both fit): byte offsets of its parts, each a multiple
-// of 256, and the total.  Per image: cap = 384 ceil(w / 8) ceil(h / 8) bytes, the 4:4:4 coefficients;
-// blocks = the scan's blocks, dummy ones included, of whichever output layout has more.
+// of 256, and the total.  Per image (jpeg_max of the output layouts): cap = the 4:4:4 coefficients'
+// bytes; blocks = the scan's blocks, dummy ones included, of whichever output layout has more.
 constexpr int kJpegeTile = 256;     // scan blocks per workgroup of the count and pack kernels
 constexpr int kJpegeChunk = 1024;   // stream bytes per workgroup of the stuffing kernels
 struct JpegeWork {
@@ -242,10 +243,9 @@ struct JpegeWork {
     size_t total;
     JpegeWork(int n, int w, int h, bool optimise = false) {
         auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-        const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
-        const size_t mcus = ((ywb + 1) / 2) * ((yhb + 1) / 2), N = static_cast<size_t>(n);
-        cap = 384 * ywb * yhb;
-        blocks = 3 * ywb * yhb > 6 * mcus ? 3 * ywb * yhb : 6 * mcus;
+        const JpegMax most = jpeg_max(w, h, false);
+        const size_t N = static_cast<size_t>(n);
+        cap = most.cap, blocks = most.blocks;
         tiles = (blocks + kJpegeTile - 1) / kJpegeTile;
         chunks = (cap + kJpegeChunk - 1) / kJpegeChunk;
         coefs = 0;
@@ -272,8 +272,7 @@ constexpr int kJpeghSeq = 256;   // lanes, so subsequences, per workgroup: a seq
 constexpr int kJpeghRounds = 2;  // launches that carry states across sequences, after the first
 // The decoder's workspace, sized without the layout like JpegeWork: byte offsets of its parts, each a
 // multiple of 256, and the total.  The statuses lead, so a plan's caller finds them at the head.
-// blocks is the most of the three input layouts: 4:2:2's 4 ceil(ywb / 2) yhb passes the other two
-// where ywb = 1 and yhb is even.
+// blocks is the most of the three input layouts (jpeg_max).
 struct JpeghWork {
     size_t cap, blocks, tiles, chunks, seqs, sstride;
     size_t status;      // n u32: MIPX_JPEGH_* per image
@@ -294,11 +293,9 @@ struct JpeghWork {
     size_t total;
     JpeghWork(int n, int w, int h) {
         auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-        const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
-        const size_t mcus = ((ywb + 1) / 2) * ((yhb + 1) / 2), N = static_cast<size_t>(n);
-        cap = 384 * ywb * yhb;
-        blocks = 3 * ywb * yhb > 6 * mcus ? 3 * ywb * yhb : 6 * mcus;
-        if (4 * ((ywb + 1) / 2) * yhb > blocks) blocks = 4 * ((ywb + 1) / 2) * yhb;
+        const JpegMax most = jpeg_max(w, h, true);
+        const size_t N = static_cast<size_t>(n);
+        cap = most.cap, blocks = most.blocks;
         tiles = (blocks + kJpeghSeq - 1) / kJpeghSeq;
         chunks = (cap + 4 * kJpeghSeq - 1) / (4 * kJpeghSeq);
         seqs = (cap + kJpeghSub * kJpeghSeq - 1) / (kJpeghSub * kJpeghSeq);
@@ -340,12 +337,6 @@ size_t plan_input_bytes(const mipx_plan *p);
 size_t plan_output_bytes(const mipx_plan *p);
 // whether a w x h scan is inside the optimised tables' rule: 64 x its blocks < 10^9
 bool jpeg_opt_in_range(int w, int h, int layout);
-
-// the layouts the engine reads (planes, coefficients, scans), and those it writes a JPEG in
-inline bool ycc_input_layout(int layout) {
-    return layout == MIPX_YCC_444 || layout == MIPX_YCC_420 || layout == MIPX_YCC_422;
-}
-inline bool ycc_output_layout(int layout) { return layout == MIPX_YCC_444 || layout == MIPX_YCC_420; }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -162,8 +162,7 @@ int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w
 
 int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                          int32_t quality, void *stream) {
-    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
-        quality < 1 || quality > 100)
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_output_layout(layout) || !jpeg_quality_ok(quality))
         return MIPX_EINVAL;
     return jpegc_launch(d_in, d_out, n, w, h, layout, quality, as_stream(stream));
 }
@@ -171,14 +170,13 @@ int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
 // The checks the four entropy-coder calls share.
 static int jpege_check(const char *what, const void *d_in, const void *d_out, const void *d_work, int32_t n, int32_t w,
                        int32_t h, int32_t layout, bool optimise) {
-    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420))
-        return MIPX_EINVAL;
+    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || !ycc_output_layout(layout)) return MIPX_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_work) & 15u) {
         set_error("%s: the workspace is not 16-byte aligned", what);
         return MIPX_EINVAL;
     }
     // byte offsets inside an image are 32-bit in the kernels
-    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+    if (!jpeg_fits_32(JpegGeom(w, h, layout), w, h)) {
         set_error("%s: image %dx%d too large (an image's bytes >= 2^32)", what, w, h);
         return MIPX_EUNSUPPORTED;
     }
@@ -201,7 +199,7 @@ static int jpegc_to_scan(const char *what, const uint8_t *d_coefs, uint8_t *d_ou
 static int rgb_to_jpeg_scan(const char *what, const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h,
                             int32_t layout, int32_t quality, bool optimise, void *d_work, void *stream,
                             uint64_t *d_dir = nullptr) {
-    if (quality < 1 || quality > 100) return MIPX_EINVAL;
+    if (!jpeg_quality_ok(quality)) return MIPX_EINVAL;
     int e = jpege_check(what, d_in, d_out, d_work, n, w, h, layout, optimise);
     if (e) return e;
     uint8_t *work = static_cast<uint8_t *>(d_work);
@@ -269,7 +267,7 @@ static int jpegh_check(const char *what, const void *d_slots, const void *d_out,
         return MIPX_EINVAL;
     }
     // bit offsets inside a scan are 32-bit in the kernels
-    if (mipx_jpegc_bytes(w, h, layout) >= (1ull << 29) || 3ull * w * h > 0xffffffffull) {
+    if (!jpeg_scan_fits_decoder(JpegGeom(w, h, layout)) || 3ull * w * h > 0xffffffffull) {
         set_error("%s: image %dx%d too large (a scan of 2^32 bits or more)", what, w, h);
         return MIPX_EUNSUPPORTED;
     }
@@ -290,8 +288,8 @@ int mipx_op_jpegh_to_jpegd(const uint8_t *d_slots, uint8_t *d_payloads, uint32_t
 int mipx_op_jpegh_to_rgb_scaled(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_status, int32_t n, int32_t file_w,
                                 int32_t file_h, int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes,
                                 void *stream) {
-    if (shrink == 0) shrink = 1;
-    if (shrink != 1 && shrink != 2 && shrink != 4 && shrink != 8) return MIPX_EINVAL;
+    shrink = jpeg_scale(shrink);
+    if (!jpeg_scale_ok(shrink)) return MIPX_EINVAL;
     int e = jpegh_check("jpeg scan to rgb", d_slots, d_out, d_status, n, file_w, file_h, layout, d_ws, ws_bytes);
     if (e) return e;
     const JpeghWork W(n, file_w, file_h);
@@ -311,7 +309,7 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
                          void *d_ws, size_t ws_bytes, void *stream) {
     if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_input_layout(layout)) return MIPX_EINVAL;
     // byte offsets inside an image are 32-bit in both kernels
-    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+    if (!jpeg_fits_32(JpegGeom(w, h, layout), w, h)) {
         set_error("jpeg coefficients to rgb: image %dx%d too large (an image's bytes >= 2^32)", w, h);
         return MIPX_EUNSUPPORTED;
     }
@@ -329,13 +327,12 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
 int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t file_w, int32_t file_h,
                                 int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes, void *stream) {
     if (shrink == 1) return mipx_op_jpegd_to_rgb(d_in, d_out, n, file_w, file_h, layout, d_ws, ws_bytes, stream);
-    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || !ycc_input_layout(layout) ||
-        (shrink != 2 && shrink != 4 && shrink != 8))
+    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || !ycc_input_layout(layout) || !jpeg_scale_ok(shrink))
         return MIPX_EINVAL;
     const int ow = static_cast<int>((static_cast<long long>(file_w) + shrink - 1) / shrink);
     const int oh = static_cast<int>((static_cast<long long>(file_h) + shrink - 1) / shrink);
     // byte offsets inside an image are 32-bit in both kernels
-    if (mipx_jpegd_bytes(file_w, file_h, layout) > 0xffffffffull || 3ull * ow * oh > 0xffffffffull) {
+    if (!jpeg_fits_32(JpegGeom(file_w, file_h, layout), ow, oh)) {
         set_error("jpeg coefficients to rgb at 1/%d: image %dx%d too large (an image's bytes >= 2^32)", shrink, file_w,
                   file_h);
         return MIPX_EUNSUPPORTED;
@@ -356,12 +353,12 @@ int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, 
 
 int mipx_op_jpeg_roundtrip(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                            int32_t quality, int32_t shrink, void *d_ws, size_t ws_bytes, void *stream) {
-    if (shrink == 0) shrink = 1;
-    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420) ||
-        quality < 1 || quality > 100 || (shrink != 1 && shrink != 2 && shrink != 4 && shrink != 8))
+    shrink = jpeg_scale(shrink);
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_output_layout(layout) || !jpeg_quality_ok(quality) ||
+        !jpeg_scale_ok(shrink))
         return MIPX_EINVAL;
     // byte offsets inside an image are 32-bit in both kernels
-    if (mipx_jpegd_bytes(w, h, layout) > 0xffffffffull || 3ull * w * h > 0xffffffffull) {
+    if (!jpeg_fits_32(JpegGeom(w, h, layout), w, h)) {
         set_error("jpeg round trip: image %dx%d too large (an image's bytes >= 2^32)", w, h);
         return MIPX_EUNSUPPORTED;
     }

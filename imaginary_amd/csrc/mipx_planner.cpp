@@ -613,90 +613,44 @@ extern "C" int mipx_plan_add_textmark(mipx_plan *plan, int32_t mask_w, int32_t m
     return MIPX_OK;
 }
 
-// ---- planar JPEG input (MIPX_OP_YCC) ---------------------------------------------
-extern "C" size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout) {
-    if (w <= 0 || h <= 0 || !mipx::ycc_input_layout(layout)) return 0;
-    const size_t cw = layout != MIPX_YCC_444 ? (static_cast<size_t>(w) + 1) / 2 : w;
-    const size_t ch = layout == MIPX_YCC_420 ? (static_cast<size_t>(h) + 1) / 2 : h;
-    return static_cast<size_t>(w) * h + 2 * cw * ch;
-}
+// ---- the JPEG steps' sizes: fields of jpeg_geom.h's struct, 0 for bad arguments -----------
+extern "C" size_t mipx_ycc_bytes(int32_t w, int32_t h, int32_t layout) { return mipx::JpegGeom(w, h, layout).plane_bytes; }
 
-size_t mipx::plan_input_bytes(const mipx_plan *p) {
-    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_YCC) return mipx_ycc_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
-    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_JPEGD) {
-        const mipx_step &s = p->steps[0];  // decoded at 1/a[1]: the payload is the a[2] x a[3] file's
-        if (s.a[1] > 1) return mipx_jpegd_bytes(s.a[2], s.a[3], s.a[0]);
-        return mipx_jpegd_bytes(p->in_w, p->in_h, s.a[0]);
-    }
-    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_JPEGH) {  // the same rule for the scan's slot
-        const mipx_step &s = p->steps[0];
-        if (s.a[1] > 1) return mipx_jpegh_bytes(s.a[2], s.a[3], s.a[0]);
-        return mipx_jpegh_bytes(p->in_w, p->in_h, s.a[0]);
-    }
-    return static_cast<size_t>(p->in_w) * p->in_h * p->in_bands;
-}
-
-extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
-    if (!plan_header_ok(plan) || !mipx::ycc_input_layout(layout)) return MIPX_EINVAL;
-    if (plan->in_bands != 3) {
-        mipx::set_error("mipx_plan_set_ycc_input: the plan takes %d bands, planar YCbCr makes 3", plan->in_bands);
-        return MIPX_EINVAL;
-    }
-    if (plan->n_steps > 0 && plan->steps[0].op == MIPX_OP_YCC) {
-        mipx::set_error("mipx_plan_set_ycc_input: the plan already takes planar input");
-        return MIPX_EINVAL;
-    }
-    if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_JPEGD || plan->steps[0].op == MIPX_OP_JPEGH)) {
-        mipx::set_error("mipx_plan_set_ycc_input: the plan already takes coefficient or scan input");
-        return MIPX_EINVAL;
-    }
-    if (plan->n_steps >= MIPX_MAX_STEPS) {
-        mipx::set_error("mipx_plan_set_ycc_input: the plan is full (MIPX_MAX_STEPS)");
-        return MIPX_EINVAL;
-    }
-    for (int i = plan->n_steps; i > 0; --i) plan->steps[i] = plan->steps[i - 1];
-    ++plan->n_steps;
-    mipx_step &s = plan->steps[0];
-    std::memset(&s, 0, sizeof(s));
-    s.op = MIPX_OP_YCC;
-    s.a[0] = layout;
-    s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = 3;
-    return MIPX_OK;
-}
-
-// ---- JPEG coefficient output (MIPX_OP_JPEGC) ---------------------------------------
 // also the size of the coefficients in an input payload, so it takes the input-only 4:2:2 too
-extern "C" size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout) {
-    if (w <= 0 || h <= 0 || !mipx::ycc_input_layout(layout)) return 0;
-    const size_t ywb = (static_cast<size_t>(w) + 7) / 8, yhb = (static_cast<size_t>(h) + 7) / 8;
-    if (layout == MIPX_YCC_444) return 128 * 3 * ywb * yhb;
-    const size_t cwb = ((static_cast<size_t>(w) + 1) / 2 + 7) / 8;
-    const size_t chb = layout == MIPX_YCC_420 ? ((static_cast<size_t>(h) + 1) / 2 + 7) / 8 : yhb;
-    return 128 * (ywb * yhb + 2 * cwb * chb);
+extern "C" size_t mipx_jpegc_bytes(int32_t w, int32_t h, int32_t layout) { return mipx::JpegGeom(w, h, layout).coef_bytes; }
+
+static size_t behind_header(size_t header, size_t coefs) { return coefs ? header + coefs : 0; }
+
+extern "C" size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout) {
+    return behind_header(MIPX_JPEGD_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout));
+}
+
+extern "C" size_t mipx_jpegh_bytes(int32_t w, int32_t h, int32_t layout) {
+    return behind_header(MIPX_JPEGH_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout));
 }
 
 // the output slots: of the layouts a JPEG is written in
 extern "C" size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout) {
-    const size_t coefs = mipx::ycc_output_layout(layout) ? mipx_jpegc_bytes(w, h, layout) : 0;
-    return coefs ? MIPX_JPEG_SCAN_HEADER_BYTES + coefs : 0;
+    return mipx::ycc_output_layout(layout) ? behind_header(MIPX_JPEG_SCAN_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout)) : 0;
 }
 
 extern "C" size_t mipx_jpeg_scan_opt_bytes(int32_t w, int32_t h, int32_t layout) {
-    const size_t coefs = mipx::ycc_output_layout(layout) ? mipx_jpegc_bytes(w, h, layout) : 0;
-    return coefs ? MIPX_JPEG_SCAN_OPT_HEADER_BYTES + coefs : 0;
+    return mipx::ycc_output_layout(layout) ? behind_header(MIPX_JPEG_SCAN_OPT_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout)) : 0;
 }
 
-// libjpeg's search for the least frequency starts at 10^9: a scan that could count that many symbols
-// into one table (64 per block at most) is outside the optimised tables' rule
+// Every layout but 4:2:0 counts as 4:4:4, the input-only 4:2:2 too: the callers reject that one themselves.
 bool mipx::jpeg_opt_in_range(int w, int h, int layout) {
-    const unsigned long long ywb = (static_cast<unsigned long long>(w) + 7) / 8, yhb = (static_cast<unsigned long long>(h) + 7) / 8;
-    const unsigned long long blocks = layout == MIPX_YCC_420 ? 6 * ((ywb + 1) / 2) * ((yhb + 1) / 2) : 3 * ywb * yhb;
-    return 64ull * blocks < 1000000000ull;
+    return jpeg_blocks_fit_opt(JpegGeom(w, h, layout == MIPX_YCC_420 ? MIPX_YCC_420 : MIPX_YCC_444).blocks);
 }
 
-extern "C" size_t mipx_jpegh_bytes(int32_t w, int32_t h, int32_t layout) {
-    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
-    return coefs ? MIPX_JPEGH_HEADER_BYTES + coefs : 0;
+size_t mipx::plan_input_bytes(const mipx_plan *p) {
+    if (p->n_steps > 0 && p->steps[0].op == MIPX_OP_YCC) return mipx_ycc_bytes(p->in_w, p->in_h, p->steps[0].a[0]);
+    if (p->n_steps > 0 && (p->steps[0].op == MIPX_OP_JPEGD || p->steps[0].op == MIPX_OP_JPEGH)) {
+        const mipx_step &s = p->steps[0];  // decoded at 1/a[1]: the payload, or the scan's slot, is the a[2] x a[3] file's
+        const int32_t fw = s.a[1] > 1 ? s.a[2] : p->in_w, fh = s.a[1] > 1 ? s.a[3] : p->in_h;
+        return s.op == MIPX_OP_JPEGD ? mipx_jpegd_bytes(fw, fh, s.a[0]) : mipx_jpegh_bytes(fw, fh, s.a[0]);
+    }
+    return static_cast<size_t>(p->in_w) * p->in_h * p->in_bands;
 }
 
 // whether the plan's last step makes its output something else than pixels
@@ -719,50 +673,38 @@ extern "C" int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[6
     return mipx::jpeg_qtables(quality, lum, chr) ? MIPX_OK : MIPX_EINVAL;
 }
 
-extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32_t quality) {
-    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
-    if (quality < 1 || quality > 100) {
-        mipx::set_error("mipx_plan_set_jpegc_output: quality %d outside 1..100", quality);
-        return MIPX_EINVAL;
-    }
-    if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
-        mipx::set_error("mipx_plan_set_jpegc_output: the plan makes %dx%dx%d, the coefficients are of 3 bands",
-                        plan->out_w, plan->out_h, plan->out_bands);
-        return MIPX_EINVAL;
-    }
-    if (ends_with_jpeg_output(plan)) {
-        mipx::set_error("mipx_plan_set_jpegc_output: the plan already gives coefficients or a scan");
-        return MIPX_EINVAL;
-    }
-    if (plan->n_steps >= MIPX_MAX_STEPS) {
-        mipx::set_error("mipx_plan_set_jpegc_output: the plan is full (MIPX_MAX_STEPS)");
-        return MIPX_EINVAL;
-    }
-    mipx_step &s = plan->steps[plan->n_steps++];
-    std::memset(&s, 0, sizeof(s));
-    s.op = MIPX_OP_JPEGC;
-    s.a[0] = layout, s.a[1] = quality;
-    s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
-    return MIPX_OK;
-}
-
-// ---- entropy-coded JPEG output (MIPX_OP_JPEGE) -----------------------------------------
-static int set_jpeg_scan_output(const char *who, mipx_plan *plan, int32_t layout, int32_t quality, bool optimise) {
-    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
-    if (quality < 1 || quality > 100) {
+// ---- JPEG output steps: MIPX_OP_JPEGC, MIPX_OP_JPEGE, MIPX_OP_JPEGRT ---------------------------
+// What the setters of the three share: their checks in the one order all of them keep, and the zeroed
+// step behind the plan's last, a[] = {layout, quality, a2}.  a2 is MIPX_OP_JPEGRT's shrink (0 for 1),
+// which only that step checks, with the 32-bit limit of its two kernels; MIPX_OP_JPEGE's "optimised",
+// which brings the 10^9 rule; 0 for MIPX_OP_JPEGC.  makes: what the step makes of 3 bands.
+static int append_jpeg_step(mipx_plan *plan, const char *who, const char *makes, int32_t op, int32_t layout,
+                            int32_t quality, int32_t a2) {
+    if (!plan_header_ok(plan) || !mipx::ycc_output_layout(layout)) return MIPX_EINVAL;
+    if (!mipx::jpeg_quality_ok(quality)) {
         mipx::set_error("%s: quality %d outside 1..100", who, quality);
         return MIPX_EINVAL;
     }
+    if (op == MIPX_OP_JPEGRT && !mipx::jpeg_scale_ok(mipx::jpeg_scale(a2))) {
+        mipx::set_error("%s: shrink %d is not 1, 2, 4 or 8", who, a2);
+        return MIPX_EINVAL;
+    }
     if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
-        mipx::set_error("%s: the plan makes %dx%dx%d, a YCbCr JPEG is of 3 bands", who, plan->out_w, plan->out_h,
-                        plan->out_bands);
+        mipx::set_error("%s: the plan makes %dx%dx%d, %s of 3 bands", who, plan->out_w, plan->out_h, plan->out_bands,
+                        makes);
+        return MIPX_EINVAL;
+    }
+    if (op == MIPX_OP_JPEGRT &&
+        !mipx::jpeg_fits_32(mipx::JpegGeom(plan->out_w, plan->out_h, layout), plan->out_w, plan->out_h)) {
+        mipx::set_error("%s: a %dx%d image's coefficients or RGB are 2^32 bytes or more", who, plan->out_w,
+                        plan->out_h);
         return MIPX_EINVAL;
     }
     if (ends_with_jpeg_output(plan)) {
         mipx::set_error("%s: the plan already gives coefficients or a scan", who);
         return MIPX_EINVAL;
     }
-    if (optimise && !mipx::jpeg_opt_in_range(plan->out_w, plan->out_h, layout)) {
+    if (op == MIPX_OP_JPEGE && a2 && !mipx::jpeg_opt_in_range(plan->out_w, plan->out_h, layout)) {
         mipx::set_error("%s: a %dx%d scan has 10^9 / 64 blocks or more", who, plan->out_w, plan->out_h);
         return MIPX_EINVAL;
     }
@@ -772,74 +714,47 @@ static int set_jpeg_scan_output(const char *who, mipx_plan *plan, int32_t layout
     }
     mipx_step &s = plan->steps[plan->n_steps++];
     std::memset(&s, 0, sizeof(s));
-    s.op = MIPX_OP_JPEGE;
-    s.a[0] = layout, s.a[1] = quality, s.a[2] = optimise ? 1 : 0;
+    s.op = op;
+    s.a[0] = layout, s.a[1] = quality, s.a[2] = a2;
     s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
     return MIPX_OK;
 }
 
+extern "C" int mipx_plan_set_jpegc_output(mipx_plan *plan, int32_t layout, int32_t quality) {
+    return append_jpeg_step(plan, "mipx_plan_set_jpegc_output", "the coefficients are", MIPX_OP_JPEGC, layout, quality, 0);
+}
+
 extern "C" int mipx_plan_set_jpeg_scan_output(mipx_plan *plan, int32_t layout, int32_t quality) {
-    return set_jpeg_scan_output("mipx_plan_set_jpeg_scan_output", plan, layout, quality, false);
+    return append_jpeg_step(plan, "mipx_plan_set_jpeg_scan_output", "a YCbCr JPEG is", MIPX_OP_JPEGE, layout, quality, 0);
 }
 
 extern "C" int mipx_plan_set_jpeg_scan_output_optimized(mipx_plan *plan, int32_t layout, int32_t quality) {
-    return set_jpeg_scan_output("mipx_plan_set_jpeg_scan_output_optimized", plan, layout, quality, true);
+    return append_jpeg_step(plan, "mipx_plan_set_jpeg_scan_output_optimized", "a YCbCr JPEG is", MIPX_OP_JPEGE, layout,
+                            quality, 1);
 }
 
-// ---- JPEG round trip (MIPX_OP_JPEGRT) ------------------------------------------------
+// the plan then makes the decoded size
 extern "C" int mipx_plan_add_jpeg_roundtrip(mipx_plan *plan, int32_t layout, int32_t quality, int32_t shrink) {
-    const char *who = "mipx_plan_add_jpeg_roundtrip";
-    if (!plan_header_ok(plan) || (layout != MIPX_YCC_444 && layout != MIPX_YCC_420)) return MIPX_EINVAL;
-    if (quality < 1 || quality > 100) {
-        mipx::set_error("%s: quality %d outside 1..100", who, quality);
-        return MIPX_EINVAL;
-    }
-    if (shrink != 0 && shrink != 1 && shrink != 2 && shrink != 4 && shrink != 8) {
-        mipx::set_error("%s: shrink %d is not 1, 2, 4 or 8", who, shrink);
-        return MIPX_EINVAL;
-    }
-    if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
-        mipx::set_error("%s: the plan makes %dx%dx%d, a YCbCr JPEG is of 3 bands", who, plan->out_w, plan->out_h,
-                        plan->out_bands);
-        return MIPX_EINVAL;
-    }
-    if (mipx_jpegd_bytes(plan->out_w, plan->out_h, layout) > 0xffffffffull ||
-        3ull * plan->out_w * plan->out_h > 0xffffffffull) {
-        mipx::set_error("%s: a %dx%d image's coefficients or RGB are 2^32 bytes or more", who, plan->out_w,
-                        plan->out_h);
-        return MIPX_EINVAL;
-    }
-    if (ends_with_jpeg_output(plan)) {
-        mipx::set_error("%s: the plan already gives coefficients or a scan", who);
-        return MIPX_EINVAL;
-    }
-    if (plan->n_steps >= MIPX_MAX_STEPS) {
-        mipx::set_error("%s: the plan is full (MIPX_MAX_STEPS)", who);
-        return MIPX_EINVAL;
-    }
-    const int32_t s1 = shrink > 1 ? shrink : 1;
-    mipx_step &s = plan->steps[plan->n_steps++];
-    std::memset(&s, 0, sizeof(s));
-    s.op = MIPX_OP_JPEGRT;
-    s.a[0] = layout, s.a[1] = quality, s.a[2] = shrink;
-    s.out_w = (plan->out_w + s1 - 1) / s1, s.out_h = (plan->out_h + s1 - 1) / s1, s.out_bands = 3;
+    const int e = append_jpeg_step(plan, "mipx_plan_add_jpeg_roundtrip", "a YCbCr JPEG is", MIPX_OP_JPEGRT, layout,
+                                   quality, shrink);
+    if (e) return e;
+    const int32_t s1 = mipx::jpeg_scale(shrink);
+    mipx_step &s = plan->steps[plan->n_steps - 1];
+    s.out_w = (plan->out_w + s1 - 1) / s1, s.out_h = (plan->out_h + s1 - 1) / s1;
     plan->out_w = s.out_w, plan->out_h = s.out_h;
     return MIPX_OK;
 }
 
-// ---- JPEG coefficient input (MIPX_OP_JPEGD) ----------------------------------------
-extern "C" size_t mipx_jpegd_bytes(int32_t w, int32_t h, int32_t layout) {
-    const size_t coefs = mipx_jpegc_bytes(w, h, layout);
-    return coefs ? MIPX_JPEGD_HEADER_BYTES + coefs : 0;
-}
-
-// shrink 1: the full-size step; 2, 4, 8: the step that decodes the file_w x file_h file at that scale.
-// op: MIPX_OP_JPEGD, or MIPX_OP_JPEGH for the same step behind the entropy decoder
-static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w, int32_t file_h,
-                           const char *who, int32_t op = MIPX_OP_JPEGD) {
+// ---- JPEG input steps: MIPX_OP_YCC, MIPX_OP_JPEGD, MIPX_OP_JPEGH ------------------------------
+// What the setters of the three share: their checks and the zeroed step in front of the plan's first.
+// shrink 1: the full-size step; 2, 4, 8: the step that decodes the file_w x file_h file at that scale
+// (MIPX_OP_JPEGD, and MIPX_OP_JPEGH for the same step behind the entropy decoder; planes come at full size)
+static int prepend_jpeg_step(mipx_plan *plan, const char *who, int32_t op, int32_t layout, int32_t shrink,
+                             int32_t file_w, int32_t file_h) {
     if (!plan_header_ok(plan) || !mipx::ycc_input_layout(layout)) return MIPX_EINVAL;
     if (plan->in_bands != 3) {
-        mipx::set_error("%s: the plan takes %d bands, a YCbCr JPEG makes 3", who, plan->in_bands);
+        mipx::set_error("%s: the plan takes %d bands, %s makes 3", who, plan->in_bands,
+                        op == MIPX_OP_YCC ? "planar YCbCr" : "a YCbCr JPEG");
         return MIPX_EINVAL;
     }
     if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_YCC || plan->steps[0].op == MIPX_OP_JPEGD ||
@@ -855,7 +770,7 @@ static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int3
         return MIPX_EINVAL;
     }
     if (shrink != 1) {
-        if (shrink != 2 && shrink != 4 && shrink != 8) {
+        if (!mipx::jpeg_scale_ok(shrink)) {
             mipx::set_error("%s: shrink %d is not 1, 2, 4 or 8", who, shrink);
             return MIPX_EINVAL;
         }
@@ -881,25 +796,29 @@ static int set_jpegd_input(mipx_plan *plan, int32_t layout, int32_t shrink, int3
     return MIPX_OK;
 }
 
+extern "C" int mipx_plan_set_ycc_input(mipx_plan *plan, int32_t layout) {
+    if (!plan) return MIPX_EINVAL;
+    return prepend_jpeg_step(plan, "mipx_plan_set_ycc_input", MIPX_OP_YCC, layout, 1, plan->in_w, plan->in_h);
+}
+
 extern "C" int mipx_plan_set_jpegd_input(mipx_plan *plan, int32_t layout) {
     if (!plan) return MIPX_EINVAL;
-    return set_jpegd_input(plan, layout, 1, plan->in_w, plan->in_h, "mipx_plan_set_jpegd_input");
+    return prepend_jpeg_step(plan, "mipx_plan_set_jpegd_input", MIPX_OP_JPEGD, layout, 1, plan->in_w, plan->in_h);
 }
 
 extern "C" int mipx_plan_set_jpegd_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
                                                 int32_t file_h) {
-    return set_jpegd_input(plan, layout, shrink, file_w, file_h, "mipx_plan_set_jpegd_input_scaled");
+    return prepend_jpeg_step(plan, "mipx_plan_set_jpegd_input_scaled", MIPX_OP_JPEGD, layout, shrink, file_w, file_h);
 }
 
-// ---- entropy-coded JPEG input (MIPX_OP_JPEGH) ---------------------------------------
 extern "C" int mipx_plan_set_jpegh_input(mipx_plan *plan, int32_t layout) {
     if (!plan) return MIPX_EINVAL;
-    return set_jpegd_input(plan, layout, 1, plan->in_w, plan->in_h, "mipx_plan_set_jpegh_input", MIPX_OP_JPEGH);
+    return prepend_jpeg_step(plan, "mipx_plan_set_jpegh_input", MIPX_OP_JPEGH, layout, 1, plan->in_w, plan->in_h);
 }
 
 extern "C" int mipx_plan_set_jpegh_input_scaled(mipx_plan *plan, int32_t layout, int32_t shrink, int32_t file_w,
                                                 int32_t file_h) {
-    return set_jpegd_input(plan, layout, shrink, file_w, file_h, "mipx_plan_set_jpegh_input_scaled", MIPX_OP_JPEGH);
+    return prepend_jpeg_step(plan, "mipx_plan_set_jpegh_input_scaled", MIPX_OP_JPEGH, layout, shrink, file_w, file_h);
 }
 
 extern "C" int mipx_plan_chain(const mipx_plan *stages, int32_t n_stages, mipx_plan *out) {
