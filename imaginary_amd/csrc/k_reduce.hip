@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "device_common.h"
+#include "lds_ops.h"
 
 namespace mipx {
 namespace {
@@ -42,18 +43,25 @@ using namespace dev;
 //    packed back to a dword and written to LDS in input byte order: one
 //    conflict-free ds_write_b32 per lane and row.
 //  * Horizontal pass: an item is K output pixels of one row; it reads the
-//    13-dword byte window it needs (ds_read_b64: lane stride 6 dwords for RGB,
-//    conflict-free; ds_read_b128 for RGBA, stride 4 dwords), converts each
-//    byte once and stores 12 (RGB) / 8 (RGBA) contiguous output bytes.
+//    13-dword byte window it needs, converts each byte once and stores 12 (RGB) / 8
+//    (RGBA) contiguous output bytes.  In the one-pass tile (reduce2_hwalk) 240 lanes each
+//    own an item column and walk down it 6 (RGB) / 4 (RGBA) rows at a time, with an LDS
+//    address and an output pointer that advance by constants; the window comes as
+//    ds_read_b64 (RGB: lane stride 6 dwords) / ds_read_b128 (RGBA: 4 dwords) with an
+//    explicit wait.  The chunk loop's reduce2_hitem derives row, column and addresses
+//    per item.
 // The intermediate never touches HBM; the 24-row LDS image is 27 KB per workgroup, and
 // both it and the registers (84 VGPRs) allow 5 workgroups per CU.
-// Schedule of a tile (reduce2_onepass, variant 66): one burst of 29 raw loads, one
+// Schedule of a tile (reduce2_onepass, variant 66): the tile's (img, band, strip) decoded
+// on the scalar unit by multiply-shift division, one burst of 29 raw loads, one
 // straight-line vertical pass over the band's 24 rows (each consumed register pair
 // refetches the row 12 ahead, every wait is a counted vmcnt), one barrier (two on strips
 // that touch the image edge), one horizontal pass; the kernel ends after its stores.  The
 // chunk-loop body it replaced (reduce2_tile: load, vertical, barrier, horizontal per
 // 12-row chunk, which drains vmcnt to 0 behind the previous chunk's stores) stays as
-// variant 578 for A/B and for MIPX_R2_BAND (profiles/r08/r2_onepass_ab.jsonl).
+// variant 578 for A/B and for MIPX_R2_BAND (profiles/r08/r2_onepass_ab.jsonl;
+// profiles/r17 for the column walk and the scalar decode, and for what was measured
+// slower: 8-pixel items stored as two halves, unguarded intermediate rows).
 // ===========================================================================
 constexpr int kR = 12;           // output rows per LDS chunk (2 ring periods)
 // WIDE level (variant bits 6 / 7): 128 << WIDE threads and strips 2x / 4x as
@@ -95,7 +103,25 @@ struct Reduce2Args {
     float c0, c1, c3, c5, bias;
     int remap;       // XCD-aware tile order (MIPX_R2_REMAP=0 disables, for A/B)
     int band_major;  // tile order inside an XCD range (MIPX_R2_ORDER=1: bands fastest)
+    // t / n_strips and t / n_bands as (t * mul) >> sh, exact for every t < 2^31
+    // (udiv_magic below): the tile decode is a few scalar multiplies
+    uint32_t strips_mul, strips_sh, bands_mul, bands_sh;
 };
+
+// floor(t / d) == (t * mul) >> sh for every t < 2^31, with l = ceil(log2 d), sh = 31 + l and
+// mul = ceil(2^sh / d) < 2^32 (d > 2^(l-1)).  Proof: mul * d = 2^sh + e with 0 <= e < d, so
+// t * mul / 2^sh = t / d + t * e / (d * 2^sh); t < 2^31 and e < d <= 2^l give
+// t * e < 2^sh, an excess below 1 / d, which cannot carry t / d over the next integer.
+inline void udiv_magic(uint32_t d, uint32_t *mul, uint32_t *sh) {
+    uint32_t l = 0;
+    while (l < 31 && (1u << l) < d) ++l;
+    *sh = 31 + l;
+    *mul = static_cast<uint32_t>(((1ull << (31 + l)) + d - 1) / d);
+}
+// on uniform operands: s_mul_i32, s_mul_hi_u32, s_lshr_b64
+__device__ __forceinline__ uint32_t udiv_by(uint32_t t, uint32_t mul, uint32_t sh) {
+    return static_cast<uint32_t>((static_cast<unsigned long long>(t) * mul) >> sh);
+}
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -217,6 +243,98 @@ __device__ __forceinline__ void reduce2_hitem(const Reduce2Args &a, int img, con
         } else {
             q32[0] = d0;
             if (full) q32[1] = d1;
+        }
+    }
+}
+
+// Horizontal pass of the one-pass tile, walked by column: reduce2_hitem's item (K pixels,
+// 13-dword window, one contiguous 12- / 8-byte store per lane) with its index arithmetic
+// hoisted.  Lane tid < IPR * RPI takes item column j = tid % IPR (IPR = 40 RGB, 60 RGBA)
+// and rows u = tid / IPR, + RPI, ... < rows (RPI = 6 / 4: 240 lanes walk 4 / 6 rows); the
+// LDS address and the output pointer are computed once and advance by constants, so no
+// division or multiply stays in the walk.  The window comes through lds_ops.h as seven
+// ds_read_b64 (RGB, 8-byte aligned start) or three ds_read_b128 and a ds_read_b64 (RGBA),
+// which the compiler cannot fuse into ds_read2_b64; the last read fetches one dword past
+// the window, still inside the row.  The tap chain and the stores are reduce2_hitem's.
+template <int B, int WIDE, int TIGHT>
+__device__ __forceinline__ void reduce2_hwalk(const Reduce2Args &a, int img, const uint32_t *lds, int x0, int y0,
+                                              int rows, float c0, float c1, float c3, float c5, float bias) {
+    using G = R2<B, WIDE, TIGHT>;
+    constexpr int K = G::K, IPR = G::TW / K, RPI = G::kThreads / IPR;
+    constexpr int W0 = (B * 2 * K) / 4;  // window start (dwords) per item
+    static_assert(W0 * (IPR - 1) + 14 <= G::kPitch, "the last read stays inside the row");
+    static_assert(B == 3 || (RPI * B) % 8 == 0, "RGBA: a walk step keeps the store alignment");
+    const int tid = threadIdx.x;
+    const int u0 = tid / IPR;
+    const int j = tid - u0 * IPR;
+    const int x = x0 + K * j;
+    if (u0 >= RPI || x >= a.x_end) return;
+    u8 *q = a.out + img * a.out_img + (static_cast<size_t>(y0 + u0) * a.ow + x) * B;
+    const size_t qstep = static_cast<size_t>(RPI) * a.ow * B;
+    uint32_t la = rc_lds(lds) + static_cast<uint32_t>(u0 * G::kPitch + W0 * j) * 4u;
+    const bool full = x + K <= a.ow;
+    for (int u = u0; u < rows; u += RPI, la += RPI * G::kPitch * 4, q += qstep) {
+        uint32_t win[14];
+        if constexpr (B == 3) {
+            rc_u2 w0 = lds_rd64_at<0>(la), w1 = lds_rd64_at<8>(la), w2 = lds_rd64_at<16>(la),
+                  w3 = lds_rd64_at<24>(la), w4 = lds_rd64_at<32>(la), w5 = lds_rd64_at<40>(la),
+                  w6 = lds_rd64_at<48>(la);
+            lgkm_wait_for<0>(w0, w1, w2, w3, w4, w5, w6);
+            win[0] = w0.x, win[1] = w0.y, win[2] = w1.x, win[3] = w1.y, win[4] = w2.x, win[5] = w2.y;
+            win[6] = w3.x, win[7] = w3.y, win[8] = w4.x, win[9] = w4.y, win[10] = w5.x, win[11] = w5.y;
+            win[12] = w6.x, win[13] = w6.y;
+        } else {
+            rc_u4 w0 = lds_rd128_at<0>(la), w1 = lds_rd128_at<16>(la), w2 = lds_rd128_at<32>(la);
+            rc_u2 w3 = lds_rd64_at<48>(la);
+            lgkm_wait_for<0>(w0, w1, w2, w3);
+            win[0] = w0.x, win[1] = w0.y, win[2] = w0.z, win[3] = w0.w, win[4] = w1.x, win[5] = w1.y;
+            win[6] = w1.z, win[7] = w1.w, win[8] = w2.x, win[9] = w2.y, win[10] = w2.z, win[11] = w2.w;
+            win[12] = w3.x, win[13] = w3.y;
+        }
+        float o[K][B];
+#pragma unroll
+        for (int c = 0; c < B; ++c) {
+            // px[t]: intermediate pixel 2x - 5 + t of channel c
+            float px[2 * K + 9];
+#pragma unroll
+            for (int t = 0; t < 2 * K + 9; ++t) {
+                const int lb = B * t + c + G::OFF0;
+                const uint32_t dd = win[lb >> 2];
+                switch (lb & 3) {
+                    case 0: px[t] = ubyte_once<0>(dd); break;
+                    case 1: px[t] = ubyte_once<1>(dd); break;
+                    case 2: px[t] = ubyte_once<2>(dd); break;
+                    default: px[t] = ubyte_once<3>(dd); break;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int m = 2 * k + 5;
+                o[k][c] = tap7(c0, c1, c3, c5, bias, px[m], px[m - 1], px[m + 1], px[m - 3], px[m + 3], px[m - 5],
+                               px[m + 5]);
+            }
+        }
+        if (B == 3) {
+            const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[1][0]);
+            const uint32_t d1 = pack4b(o[1][1], o[1][2], o[2][0], o[2][1]);
+            const uint32_t d2 = pack4b(o[2][2], o[3][0], o[3][1], o[3][2]);
+            if (full && (reinterpret_cast<uintptr_t>(q) & 3u) == 0) {
+                *reinterpret_cast<uint3 *>(q) = uint3{d0, d1, d2};
+            } else {
+                const uint32_t dd[3] = {d0, d1, d2};
+                const int nb = (full ? K : a.ow - x) * B;
+                for (int i = 0; i < nb; ++i) q[i] = static_cast<u8>(dd[i >> 2] >> (8 * (i & 3)));
+            }
+        } else {
+            const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[0][3]);
+            const uint32_t d1 = pack4b(o[1][0], o[1][1], o[1][2], o[1][3]);
+            uint32_t *q32 = reinterpret_cast<uint32_t *>(q);
+            if (full && (reinterpret_cast<uintptr_t>(q) & 7u) == 0) {
+                *reinterpret_cast<uint2 *>(q) = uint2{d0, d1};
+            } else {
+                q32[0] = d0;
+                if (full) q32[1] = d1;
+            }
         }
     }
 }
@@ -404,7 +522,7 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
                                                 uint32_t *lds) {
     using G = R2<B, WIDE, TIGHT>;
     constexpr int kThreads = G::kThreads, kPitch = G::kPitch;
-    constexpr int TW = G::TW, K = G::K;
+    constexpr int TW = G::TW;
     const int tid = threadIdx.x;
     const int x0 = (a.s_base + strip) * TW;
     const int row_bytes = a.w * B;
@@ -447,16 +565,8 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
         }
     }
     __syncthreads();
-    // ---- horizontal pass: K output pixels per item, one channel at a time ----
-    constexpr int items_per_row = TW / K;
-    for (int it = tid; it < rows * items_per_row; it += kThreads) {
-        const int u = it / items_per_row;
-        const int j = it - u * items_per_row;
-        const int x = x0 + K * j;
-        const int y = y0 + u;
-        if (x >= a.x_end) continue;
-        reduce2_hitem<B, WIDE, TIGHT, false, false>(a, img, lds + u * kPitch, j, x, y, c0, c1, c3, c5, bias);
-    }
+    // ---- horizontal pass: 2 K output pixels per item, lanes walk down item columns ----
+    reduce2_hwalk<B, WIDE, TIGHT>(a, img, lds, x0, y0, rows, c0, c1, c3, c5, bias);
 }
 
 // The centre sampling convention's 2 x 2 reduce is k_reduce2m (k_reduce2m.hip); its
@@ -474,7 +584,8 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
 // bit 9: the chunk-loop body reduce2_tile (the bits above select its build); without it
 // the one-pass body reduce2_onepass at this strip width, which is R = 12 with prefetch.
 template <int B, int VAR>
-__global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kThreads) k_reduce2x2(Reduce2Args a) {
+__global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kThreads) 
+    k_reduce2x2(Reduce2Args a) {
     constexpr int WIDE = (VAR & 128) ? 2 : (VAR & 64) ? 1 : 0;
     constexpr int TIGHT = (VAR & 256) ? 1 : 0;
     constexpr int kPitch = R2T<WIDE, TIGHT>::kPitch;
@@ -484,19 +595,22 @@ __global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kTh
     constexpr bool MEM = (VAR & 8) != 0;
     constexpr int LAUX = (VAR & 16) ? 2 : 0;  // bit 4: non-temporal loads (cache policy nt)
     constexpr bool NTS = (VAR & 32) != 0;     // bit 5: non-temporal stores
-    __shared__ uint32_t lds[2 * R * kPitch];
+    __shared__ __attribute__((aligned(16))) uint32_t lds[2 * R * kPitch];
     const uint32_t t = a.remap ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    // t -> (img, band, strip) by exact multiply-shift division: all uniform, so it stays on
+    // the scalar unit (a plain / would go through the vector float reciprocal, and every
+    // load address waits on it)
     int strip, band, img;
     if (a.band_major) {  // tiles ordered (img, strip, band): vertical neighbours adjacent
-        band = t % a.n_bands;
-        const int rest = t / a.n_bands;
-        strip = rest % a.n_strips;
-        img = rest / a.n_strips;
+        const uint32_t rest = udiv_by(t, a.bands_mul, a.bands_sh);
+        band = static_cast<int>(t - rest * static_cast<uint32_t>(a.n_bands));
+        img = static_cast<int>(udiv_by(rest, a.strips_mul, a.strips_sh));
+        strip = static_cast<int>(rest - static_cast<uint32_t>(img) * static_cast<uint32_t>(a.n_strips));
     } else {             // (img, band, strip): horizontal neighbours adjacent
-        strip = t % a.n_strips;
-        const int rest = t / a.n_strips;
-        band = rest % a.n_bands;
-        img = rest / a.n_bands;
+        const uint32_t rest = udiv_by(t, a.strips_mul, a.strips_sh);
+        strip = static_cast<int>(t - rest * static_cast<uint32_t>(a.n_strips));
+        img = static_cast<int>(udiv_by(rest, a.bands_mul, a.bands_sh));
+        band = static_cast<int>(rest - static_cast<uint32_t>(img) * static_cast<uint32_t>(a.n_bands));
     }
     if constexpr ((VAR & 512) != 0) {
         reduce2_tile<B, R, PF, PK, MEM, LAUX, NTS, WIDE, TIGHT>(a, img, strip, band, lds);
@@ -737,7 +851,9 @@ int reduce2_window_launch(const u8 *in, u8 *out, int n, int w, int h, int b, int
     const char *eo = tune_env("MIPX_R2_ORDER");
     a.band_major = (eo && *eo) ? std::atoi(eo) : 0;
     const long long tiles = static_cast<long long>(a.n_strips) * a.n_bands * n;
-    if (tiles > 0x7fffffffLL) return MIPX_EINVAL;
+    if (tiles > 0x7fffffffLL) return MIPX_EINVAL;  // also what the decode's divisions rely on
+    udiv_magic(static_cast<uint32_t>(a.n_strips), &a.strips_mul, &a.strips_sh);
+    udiv_magic(static_cast<uint32_t>(a.n_bands), &a.bands_mul, &a.bands_sh);
     dim3 grid(static_cast<unsigned>(tiles));
 #define MIPX_R2(V)                                                                                      \
     case V: {                                                                                           \

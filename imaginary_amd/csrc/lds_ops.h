@@ -69,6 +69,22 @@ __device__ __forceinline__ rc_u4 lds_rd128(uint32_t a) {
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a));
     return v;
 }
+// The same reads at a constant byte offset from one address register (the instruction's
+// 16-bit offset field): a window of several pieces costs no address arithmetic
+template <int OFF>
+__device__ __forceinline__ rc_u4 lds_rd128_at(uint32_t a) {
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 16 == 0, "ds_read_b128 offset");
+    rc_u4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "n"(OFF));
+    return v;
+}
+template <int OFF>
+__device__ __forceinline__ rc_u2 lds_rd64_at(uint32_t a) {
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds_read_b64 offset");
+    rc_u2 v;
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(a), "n"(OFF));
+    return v;
+}
 __device__ __forceinline__ rc_v2i lds_tr8(uint32_t a) {
     rc_v2i v;
     asm volatile("ds_read_b64_tr_b8 %0, %1" : "=v"(v) : "v"(a));
