@@ -53,7 +53,8 @@ using namespace dev;
 // The intermediate never touches HBM; the 24-row LDS image is 27 KB per workgroup, and
 // both it and the registers (84 VGPRs) allow 5 workgroups per CU.
 // Schedule of a tile (reduce2_onepass, variant 66): the tile's (img, band, strip) decoded
-// on the scalar unit by multiply-shift division, one burst of 29 raw loads, one
+// on the scalar unit by multiply-shift division, one burst of 29 raw loads (s_setprio 2 from
+// kernel entry to the burst's 17th load: profiles/r18), one
 // straight-line vertical pass over the band's 24 rows (each consumed register pair
 // refetches the row 12 ahead, every wait is a counted vmcnt), one barrier (two on strips
 // that touch the image edge), one horizontal pass; the kernel ends after its stores.  The
@@ -483,6 +484,9 @@ __device__ __forceinline__ void reduce2_vpass(const LoadRow &load_row, int y0, i
     for (int u = 0; u < R; ++u) {
         odd[u] = load_row(2 * (y0 + u + 2) + 1);
         even[u] = load_row(2 * (y0 + u));
+        // the kernel raised this wave's priority at entry; 17 of the burst's 29 loads are out, the
+        // rest go at the priority of the waves that compute (measured best, profiles/r18)
+        if (u == R / 2 - 1) __builtin_amdgcn_s_setprio(0);
     }
     // odd-row ring: slot s holds odd row 2m+1 with m = s (mod 6); y0 % 6 == 0
     f4v ring[6];
@@ -596,6 +600,10 @@ __global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kTh
     constexpr int LAUX = (VAR & 16) ? 2 : 0;  // bit 4: non-temporal loads (cache policy nt)
     constexpr bool NTS = (VAR & 32) != 0;     // bit 5: non-temporal stores
     __shared__ __attribute__((aligned(16))) uint32_t lds[2 * R * kPitch];
+    // One-pass body: a new tile is the youngest wave on its SIMD and would queue for issue behind
+    // the older waves' arithmetic; it runs above them through the tile decode and the first 17
+    // loads of its burst (reduce2_vpass lowers it again), so its rows are on their way early
+    if constexpr ((VAR & 512) == 0) __builtin_amdgcn_s_setprio(2);
     const uint32_t t = a.remap ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
     // t -> (img, band, strip) by exact multiply-shift division: all uniform, so it stays on
     // the scalar unit (a plain / would go through the vector float reciprocal, and every
