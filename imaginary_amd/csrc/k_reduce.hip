@@ -17,6 +17,7 @@
 
 #include "device_common.h"
 #include "lds_ops.h"
+#include "reduce2_geom.h"
 
 namespace mipx {
 namespace {
@@ -34,60 +35,33 @@ using namespace dev;
 // The host verifies that shape on the actual integer table before choosing
 // this kernel, so the arithmetic is exactly libvips' 13-tap sum.
 //
-// One workgroup = a strip of TW output pixels x a band of rows.
-//  * Vertical pass: lane t owns dword t of the strip's input bytes (channel
-//    agnostic) and walks down the band with the six odd rows of the current
-//    window in a static register ring (slot = odd-row index mod 6, unrolled
-//    by 12); each input byte is loaded and converted once.  The rounded uchar
-//    intermediate (libvips materialises it between reducev and reduceh) is
-//    packed back to a dword and written to LDS in input byte order: one
-//    conflict-free ds_write_b32 per lane and row.
-//  * Horizontal pass: an item is K output pixels of one row; it reads the
-//    13-dword byte window it needs, converts each byte once and stores 12 (RGB) / 8
-//    (RGBA) contiguous output bytes.  In the one-pass tile (reduce2_hwalk) 240 lanes each
-//    own an item column and walk down it 6 (RGB) / 4 (RGBA) rows at a time, with an LDS
-//    address and an output pointer that advance by constants; the window comes as
-//    ds_read_b64 (RGB: lane stride 6 dwords) / ds_read_b128 (RGBA: 4 dwords) with an
-//    explicit wait.  The chunk loop's reduce2_hitem derives row, column and addresses
-//    per item.
+// One workgroup (256 lanes) = one tile: a strip of TW = 160 (RGB) / 120 (RGBA) output
+// pixels x a band of 24 output rows; the constants and the launch of a window are
+// reduce2_geom.h's.
+//  * Vertical pass (reduce2_vpass): lane t owns dword t of the strip's input bytes
+//    (channel agnostic) and walks down the band with the six odd rows of the current
+//    window in a static register ring (slot = odd-row index mod 6); each input byte is
+//    loaded and converted once.  The rounded uchar intermediate (libvips materialises it
+//    between reducev and reduceh) is packed back to a dword and written to LDS in input
+//    byte order: one conflict-free ds_write_b32 per lane and row.
+//  * Horizontal pass (reduce2_hwalk): an item is K = 4 / 2 output pixels of one row; it
+//    reads the 13-dword byte window it needs, converts each byte once and stores 12 / 8
+//    contiguous output bytes.  240 lanes each own an item column and walk down it 6 / 4
+//    rows at a time, with an LDS address and an output pointer that advance by constants;
+//    the window comes as ds_read_b64 (RGB: lane stride 6 dwords) / ds_read_b128 (RGBA: 4
+//    dwords) with an explicit wait.
 // The intermediate never touches HBM; the 24-row LDS image is 27 KB per workgroup, and
 // both it and the registers (84 VGPRs) allow 5 workgroups per CU.
-// Schedule of a tile (reduce2_onepass, variant 66): the tile's (img, band, strip) decoded
-// on the scalar unit by multiply-shift division, one burst of 29 raw loads (s_setprio 2 from
-// kernel entry to the burst's 17th load: profiles/r18), one
-// straight-line vertical pass over the band's 24 rows (each consumed register pair
-// refetches the row 12 ahead, every wait is a counted vmcnt), one barrier (two on strips
-// that touch the image edge), one horizontal pass; the kernel ends after its stores.  The
-// chunk-loop body it replaced (reduce2_tile: load, vertical, barrier, horizontal per
-// 12-row chunk, which drains vmcnt to 0 behind the previous chunk's stores) stays as
-// variant 578 for A/B and for MIPX_R2_BAND (profiles/r08/r2_onepass_ab.jsonl;
-// profiles/r17 for the column walk and the scalar decode, and for what was measured
-// slower: 8-pixel items stored as two halves, unguarded intermediate rows).
+// Schedule of a tile (reduce2_onepass): the tile's (img, band, strip) decoded on the scalar
+// unit by multiply-shift division, one burst of 29 raw loads (s_setprio 2 from kernel entry
+// to the burst's 17th load: profiles/r18), one straight-line vertical pass over the band's
+// 24 rows (each consumed register pair refetches the row 12 ahead, every wait is a counted
+// vmcnt), one barrier (two on strips that touch the image edge), one horizontal pass; the
+// kernel ends after its stores, so no wait covers a store.  What else was built and
+// measured (other strip widths and LDS pitches, packed taps, cache hints, a loop over
+// 12-row chunks) is DESIGN 4.1's to tell.
 // ===========================================================================
-constexpr int kR = 12;           // output rows per LDS chunk (2 ring periods)
-// WIDE level (variant bits 6 / 7): 128 << WIDE threads and strips 2x / 4x as
-// wide (less relative halo, longer contiguous row segments, fewer workgroups)
-// TIGHT (variant bit 8, WIDE 1 only): rows 264 dwords apart (== 8 mod 64) instead of 288,
-// 25.3 instead of 27.6 KB of LDS, so 6 workgroups share a CU instead of 5 (r02 A/B)
-template <int WIDE, int TIGHT = 0>
-struct R2T {
-    static constexpr int kThreads = 128 << WIDE;
-    static constexpr int kPitch = WIDE == 2 ? 544 : WIDE == 1 ? (TIGHT ? 264 : 288) : 160;  // LDS dwords per row
-};
-
-template <int B, int WIDE = 0, int TIGHT = 0>
-struct R2 {
-    static constexpr int kThreads = R2T<WIDE, TIGHT>::kThreads;
-    static constexpr int kPitch = R2T<WIDE, TIGHT>::kPitch;
-    static constexpr int TW = B == 3 ? 80 << WIDE : WIDE == 0 ? 56 : 60 << WIDE;  // output pixels per strip
-    static constexpr int NPX = 2 * TW + 9;           // intermediate px 2x0-5 .. 2x0+2TW+3
-    static constexpr int K = B == 3 ? 4 : 2;         // output pixels per horizontal item
-    static constexpr int OFF0 = B == 3 ? 1 : 0;      // B*(2x0-5) - floor4(B*(2x0-5))
-    static constexpr int ND = (B * NPX + OFF0 + 3) / 4;  // dwords per row
-    static_assert(ND <= kThreads && ND <= kPitch, "strip too wide");
-    static_assert(((TW / K) * K) == TW, "items must tile the strip");
-    static_assert((B * 2 * K) % 8 == 0, "window start must be 8-byte aligned");
-};
+constexpr int kR = kReduce2ChunkRows;  // output rows per load round (2 ring periods)
 
 struct Reduce2Args {
     const u8 *in;
@@ -124,14 +98,11 @@ __device__ __forceinline__ uint32_t udiv_by(uint32_t t, uint32_t mul, uint32_t s
     return static_cast<uint32_t>((static_cast<unsigned long long>(t) * mul) >> sh);
 }
 
-typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f4v cvt4_once(uint32_t v) {
     return f4v{ubyte_once<0>(v), ubyte_once<1>(v), ubyte_once<2>(v), ubyte_once<3>(v)};
 }
-__device__ __forceinline__ f2v lo2(f4v v) { return __builtin_shufflevector(v, v, 0, 1); }
-__device__ __forceinline__ f2v hi2(f4v v) { return __builtin_shufflevector(v, v, 2, 3); }
 
 // c0 e + c1 (m1 + p1) + c3 (m3 + p3) + c5 (m5 + p5) with pre-scaled taps and the
 // bias: every partial is exact on a 1/8192 grid below 2^9, so the result is
@@ -143,15 +114,6 @@ __device__ __forceinline__ float tap7(float c0, float c1, float c3, float c5, fl
     acc = __builtin_fmaf(c3, m3 + p3, acc);
     return __builtin_fmaf(c5, m5 + p5, acc);
 }
-// the same chain on two columns at once (v_pk_fma_f32 / v_pk_add_f32): each lane
-// of the pair sees exactly the scalar operation sequence, so results are identical
-__device__ __forceinline__ f2v tap7v(f2v c0, f2v c1, f2v c3, f2v c5, f2v bias, f2v e, f2v m1, f2v p1, f2v m3,
-                                     f2v p3, f2v m5, f2v p5) {
-    f2v acc = __builtin_elementwise_fma(c0, e, bias);
-    acc = __builtin_elementwise_fma(c1, m1 + p1, acc);
-    acc = __builtin_elementwise_fma(c3, m3 + p3, acc);
-    return __builtin_elementwise_fma(c5, m5 + p5, acc);
-}
 // v_cvt_pk_u8_f32 rounds to nearest-even and saturates to 0..255; on the
 // 1/4096 grid RNE(sum/4096 + 2^-13) == floor(sum/4096 + 0.5) (no ties occur)
 __device__ __forceinline__ uint32_t pack4b(float a, float b, float c, float d) {
@@ -161,110 +123,21 @@ __device__ __forceinline__ uint32_t pack4b(float a, float b, float c, float d) {
     return __builtin_amdgcn_cvt_pk_u8_f32(d, 3, v);
 }
 
-// One horizontal item: K output pixels of output row y from column x (item j of the
-// strip), read from the LDS row `row` of packed intermediate bytes.
-template <int B, int WIDE, int TIGHT, bool MEM, bool NTS>
-__device__ __forceinline__ void reduce2_hitem(const Reduce2Args &a, int img, const uint32_t *row, int j, int x,
-                                              int y, float c0, float c1, float c3, float c5, float bias) {
-    using G = R2<B, WIDE, TIGHT>;
-    constexpr int K = G::K;
-    constexpr int W0 = (B * 2 * K) / 4;  // window start (dwords) per item
-    uint32_t win[13];
-    if (B == 3) {
-        const uint2 *r2 = reinterpret_cast<const uint2 *>(row + W0 * j);
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const uint2 dd = r2[q];
-            win[2 * q] = dd.x;
-            win[2 * q + 1] = dd.y;
-        }
-        win[12] = row[W0 * j + 12];
-    } else {
-        const uint4 *r4 = reinterpret_cast<const uint4 *>(row + W0 * j);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const uint4 dd = r4[q];
-            win[4 * q] = dd.x, win[4 * q + 1] = dd.y, win[4 * q + 2] = dd.z, win[4 * q + 3] = dd.w;
-        }
-        win[12] = row[W0 * j + 12];
-    }
-    float o[K][B];
-    if (MEM) {  // diagnostic: skip the arithmetic, keep the LDS reads and stores
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-#pragma unroll
-            for (int c = 0; c < B; ++c) o[k][c] = __uint_as_float(win[(k * B + c) % 13] & 0x437f0000u);
-    } else
-#pragma unroll
-    for (int c = 0; c < B; ++c) {
-        // px[t]: intermediate pixel 2x - 5 + t of channel c
-        float px[2 * K + 9];
-#pragma unroll
-        for (int t = 0; t < 2 * K + 9; ++t) {
-            const int lb = B * t + c + G::OFF0;
-            const uint32_t dd = win[lb >> 2];
-            switch (lb & 3) {
-                case 0: px[t] = ubyte_once<0>(dd); break;
-                case 1: px[t] = ubyte_once<1>(dd); break;
-                case 2: px[t] = ubyte_once<2>(dd); break;
-                default: px[t] = ubyte_once<3>(dd); break;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int m = 2 * k + 5;
-            o[k][c] = tap7(c0, c1, c3, c5, bias, px[m], px[m - 1], px[m + 1], px[m - 3], px[m + 3], px[m - 5],
-                           px[m + 5]);
-        }
-    }
-    u8 *q = a.out + img * a.out_img + (static_cast<size_t>(y) * a.ow + x) * B;
-    const bool full = x + K <= a.ow;
-    if (B == 3) {
-        const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[1][0]);
-        const uint32_t d1 = pack4b(o[1][1], o[1][2], o[2][0], o[2][1]);
-        const uint32_t d2 = pack4b(o[2][2], o[3][0], o[3][1], o[3][2]);
-        if (full && (reinterpret_cast<uintptr_t>(q) & 3u) == 0) {
-            if (NTS) {
-                typedef uint32_t u3v __attribute__((ext_vector_type(3)));
-                __builtin_nontemporal_store(u3v{d0, d1, d2}, reinterpret_cast<u3v *>(q));
-            } else {
-                *reinterpret_cast<uint3 *>(q) = uint3{d0, d1, d2};
-            }
-        } else {
-            const uint32_t dd[3] = {d0, d1, d2};
-            const int nb = (full ? K : a.ow - x) * B;
-            for (int i = 0; i < nb; ++i) q[i] = static_cast<u8>(dd[i >> 2] >> (8 * (i & 3)));
-        }
-    } else {
-        const uint32_t d0 = pack4b(o[0][0], o[0][1], o[0][2], o[0][3]);
-        const uint32_t d1 = pack4b(o[1][0], o[1][1], o[1][2], o[1][3]);
-        uint32_t *q32 = reinterpret_cast<uint32_t *>(q);
-        if (full && (reinterpret_cast<uintptr_t>(q) & 7u) == 0) {
-            *reinterpret_cast<uint2 *>(q) = uint2{d0, d1};
-        } else {
-            q32[0] = d0;
-            if (full) q32[1] = d1;
-        }
-    }
-}
-
-// Horizontal pass of the one-pass tile, walked by column: reduce2_hitem's item (K pixels,
-// 13-dword window, one contiguous 12- / 8-byte store per lane) with its index arithmetic
-// hoisted.  Lane tid < IPR * RPI takes item column j = tid % IPR (IPR = 40 RGB, 60 RGBA)
+// Horizontal pass of the tile, walked by column.  An item is K output pixels of one row: a
+// 13-dword window of packed intermediate bytes, each converted once, and one contiguous 12- /
+// 8-byte store per lane (bytewise where the row's end clips the item or the address is
+// unaligned).  Lane tid < IPR * RPI takes item column j = tid % IPR (IPR = 40 RGB, 60 RGBA)
 // and rows u = tid / IPR, + RPI, ... < rows (RPI = 6 / 4: 240 lanes walk 4 / 6 rows); the
 // LDS address and the output pointer are computed once and advance by constants, so no
 // division or multiply stays in the walk.  The window comes through lds_ops.h as seven
 // ds_read_b64 (RGB, 8-byte aligned start) or three ds_read_b128 and a ds_read_b64 (RGBA),
 // which the compiler cannot fuse into ds_read2_b64; the last read fetches one dword past
-// the window, still inside the row.  The tap chain and the stores are reduce2_hitem's.
-template <int B, int WIDE, int TIGHT>
+// the window, still inside the row.
+template <int B>
 __device__ __forceinline__ void reduce2_hwalk(const Reduce2Args &a, int img, const uint32_t *lds, int x0, int y0,
                                               int rows, float c0, float c1, float c3, float c5, float bias) {
-    using G = R2<B, WIDE, TIGHT>;
-    constexpr int K = G::K, IPR = G::TW / K, RPI = G::kThreads / IPR;
-    constexpr int W0 = (B * 2 * K) / 4;  // window start (dwords) per item
-    static_assert(W0 * (IPR - 1) + 14 <= G::kPitch, "the last read stays inside the row");
-    static_assert(B == 3 || (RPI * B) % 8 == 0, "RGBA: a walk step keeps the store alignment");
+    using G = Reduce2Geom<B>;
+    constexpr int K = G::K, IPR = G::IPR, RPI = G::RPI, W0 = G::W0, kPitch = kReduce2Pitch;
     const int tid = threadIdx.x;
     const int u0 = tid / IPR;
     const int j = tid - u0 * IPR;
@@ -272,9 +145,9 @@ __device__ __forceinline__ void reduce2_hwalk(const Reduce2Args &a, int img, con
     if (u0 >= RPI || x >= a.x_end) return;
     u8 *q = a.out + img * a.out_img + (static_cast<size_t>(y0 + u0) * a.ow + x) * B;
     const size_t qstep = static_cast<size_t>(RPI) * a.ow * B;
-    uint32_t la = rc_lds(lds) + static_cast<uint32_t>(u0 * G::kPitch + W0 * j) * 4u;
+    uint32_t la = rc_lds(lds) + static_cast<uint32_t>(u0 * kPitch + W0 * j) * 4u;
     const bool full = x + K <= a.ow;
-    for (int u = u0; u < rows; u += RPI, la += RPI * G::kPitch * 4, q += qstep) {
+    for (int u = u0; u < rows; u += RPI, la += RPI * kPitch * 4, q += qstep) {
         uint32_t win[14];
         if constexpr (B == 3) {
             rc_u2 w0 = lds_rd64_at<0>(la), w1 = lds_rd64_at<8>(la), w2 = lds_rd64_at<16>(la),
@@ -340,143 +213,16 @@ __device__ __forceinline__ void reduce2_hwalk(const Reduce2Args &a, int img, con
     }
 }
 
-template <int B, int R, bool PF, bool PK, bool MEM, int LAUX, bool NTS, int WIDE, int TIGHT>
-__device__ __forceinline__ void reduce2_tile(const Reduce2Args &a, int img, int strip, int band,
-                                             uint32_t *lds) {
-    using G = R2<B, WIDE, TIGHT>;
-    constexpr int kThreads = G::kThreads, kPitch = G::kPitch;
-    constexpr int TW = G::TW, K = G::K;
-    const int tid = threadIdx.x;
-    const int x0 = (a.s_base + strip) * TW;
-    const int row_bytes = a.w * B;
-    const int px0 = 2 * x0 - 5;          // first intermediate pixel of the strip
-    const int base = (B * px0) & ~3;     // floor to a dword (two's complement)
-    const int byte0 = base + 4 * tid;
-    const bool vlane = tid < G::ND && byte0 >= 0 && byte0 + 4 <= row_bytes;
-    // raw buffer loads: per-lane byte offset in voffset, row offset in soffset;
-    // lanes outside the row get an out-of-range voffset and read 0
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<u8 *>(a.in + img * a.in_img), 0, static_cast<int>(a.in_img), 0x00020000);
-    const uint32_t voff = vlane ? static_cast<uint32_t>(byte0) : 0x80000000u;
-    const int y0 = a.y_base + band * a.band_rows;
-    const int y1 = min(y0 + a.band_rows, a.y_end);
-    const float c0 = a.c0, c1 = a.c1, c3 = a.c3, c5 = a.c5, bias = a.bias;
-    // strip pixels outside the image (COPY edge): LDS pixels [0, nl) copy pixel 0,
-    // [fr, fr_end] copy pixel w-1; filled after each vertical pass
-    const int nl = px0 < 0 ? -px0 : 0;
-    const int x_last = min(x0 + TW, a.x_end) - 1;
-    const int fr = a.w - px0;                                   // LDS index of pixel w
-    const int fr_end = min(2 * x_last + 5 - px0, G::NPX - 1);   // last LDS pixel read
-    const int nr = fr_end >= fr ? fr_end - fr + 1 : 0;
-    const bool edge = nl > 0 || nr > 0;
-
-    auto load_row = [&](int r) -> uint32_t {
-        r = clampi(r, 0, a.h - 1);
-        return static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, r * row_bytes, LAUX));
-    };
-
-    // odd-row ring: slot s holds odd row 2m+1 with m = s (mod 6); y0 % 6 == 0
-    f4v ring[6];
-    ring[3] = cvt4_once(load_row(2 * (y0 - 3) + 1));
-    ring[4] = cvt4_once(load_row(2 * (y0 - 2) + 1));
-    ring[5] = cvt4_once(load_row(2 * (y0 - 1) + 1));
-    ring[0] = cvt4_once(load_row(2 * y0 + 1));
-    ring[1] = cvt4_once(load_row(2 * (y0 + 1) + 1));
-    ring[2] = f4v{0.f, 0.f, 0.f, 0.f};
-
-    uint32_t odd[R], even[R];
-    if (PF) {
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            odd[u] = load_row(2 * (y0 + u + 2) + 1);
-            even[u] = load_row(2 * (y0 + u));
-        }
-    }
-    int buf = 0;
-    for (int yc = y0; yc < y1; yc += R, buf ^= 1) {
-        uint32_t *L = lds + buf * (R * kPitch);
-        // ---- vertical pass: R intermediate rows -> LDS (packed uchar) ----
-        if (!PF) {
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-                odd[u] = load_row(2 * (yc + u + 2) + 1);
-                even[u] = load_row(2 * (yc + u));
-            }
-        }
-        const bool more = yc + R < y1;
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            uint32_t d;
-            if (MEM) {  // diagnostic: same loads / LDS / stores, no arithmetic
-                d = odd[u] + even[u];
-                if (PF && more) {
-                    odd[u] = load_row(2 * (yc + R + u + 2) + 1);
-                    even[u] = load_row(2 * (yc + R + u));
-                }
-            } else {
-                ring[(u + 2) % 6] = cvt4_once(odd[u]);
-                const f4v e = cvt4_once(even[u]);
-                if (PF && more) {  // rotate: this register now fetches the next chunk's row
-                    odd[u] = load_row(2 * (yc + R + u + 2) + 1);
-                    even[u] = load_row(2 * (yc + R + u));
-                }
-                const f4v m5 = ring[(u + 3) % 6], m3 = ring[(u + 4) % 6], m1 = ring[(u + 5) % 6];
-                const f4v p1 = ring[u % 6], p3 = ring[(u + 1) % 6], p5 = ring[(u + 2) % 6];
-                if (PK) {
-                    const f2v C0 = {c0, c0}, C1 = {c1, c1}, C3 = {c3, c3}, C5 = {c5, c5}, BI = {bias, bias};
-                    const f2v a = tap7v(C0, C1, C3, C5, BI, lo2(e), lo2(m1), lo2(p1), lo2(m3), lo2(p3), lo2(m5),
-                                        lo2(p5));
-                    const f2v b = tap7v(C0, C1, C3, C5, BI, hi2(e), hi2(m1), hi2(p1), hi2(m3), hi2(p3), hi2(m5),
-                                        hi2(p5));
-                    d = pack4b(a.x, a.y, b.x, b.y);
-                } else {
-                    d = pack4b(tap7(c0, c1, c3, c5, bias, e.x, m1.x, p1.x, m3.x, p3.x, m5.x, p5.x),
-                               tap7(c0, c1, c3, c5, bias, e.y, m1.y, p1.y, m3.y, p3.y, m5.y, p5.y),
-                               tap7(c0, c1, c3, c5, bias, e.z, m1.z, p1.z, m3.z, p3.z, m5.z, p5.z),
-                               tap7(c0, c1, c3, c5, bias, e.w, m1.w, p1.w, m3.w, p3.w, m5.w, p5.w));
-                }
-            }
-            if (G::ND >= kThreads || tid < G::ND) L[u * kPitch + tid] = d;
-        }
-        if (edge) {  // replicate the edge pixels (EXTEND_COPY) inside the LDS image
-            __syncthreads();
-            u8 *Lb = reinterpret_cast<u8 *>(L);
-            const int nfill = nl + nr;
-            for (int i = tid; i < R * nfill * B; i += kThreads) {
-                const int u = i / (nfill * B);
-                const int rem = i - u * nfill * B;
-                const int f = rem / B, c = rem - f * B;
-                const int dst = f < nl ? f : fr + (f - nl);
-                const int srcp = f < nl ? nl : fr - 1;
-                Lb[u * kPitch * 4 + B * dst + G::OFF0 + c] = Lb[u * kPitch * 4 + B * srcp + G::OFF0 + c];
-            }
-        }
-        __syncthreads();
-        // ---- horizontal pass: K output pixels per item, one channel at a time ----
-        constexpr int items_per_row = TW / K;
-        for (int it = tid; it < R * items_per_row; it += kThreads) {
-            const int u = it / items_per_row;
-            const int j = it - u * items_per_row;
-            const int x = x0 + K * j;
-            const int y = yc + u;
-            if (y >= a.y_end || x >= a.x_end) continue;
-            reduce2_hitem<B, WIDE, TIGHT, MEM, NTS>(a, img, L + u * kPitch, j, x, y, c0, c1, c3, c5, bias);
-        }
-        // double-buffered LDS: the next vertical pass writes the other buffer, whose
-        // readers all finished before this chunk's barrier
-    }
-}
-
-// Vertical pass of the one-pass tile over NR (12 or 24) output rows from y0: one burst
-// of raw loads (the five ring rows and the first 12 odd / even pairs, nothing converted
-// before all are issued), then NR rows of straight-line code.  A consumed register pair
-// is refilled with the row 12 ahead while rows remain, so the 24-row pass keeps 24
-// loads in flight and every wait is a counted one.
-template <int NR, int ND, int kThreads, int kPitch, class LoadRow>
+// Vertical pass of the tile over NR (12 or 24) output rows from y0: one burst of raw
+// loads (the five ring rows and the first 12 odd / even pairs, nothing converted before
+// all are issued), then NR rows of straight-line code.  A consumed register pair is
+// refilled with the row 12 ahead while rows remain, so the 24-row pass keeps 24 loads
+// in flight and every wait is a counted one.
+template <int B, int NR, class LoadRow>
 __device__ __forceinline__ void reduce2_vpass(const LoadRow &load_row, int y0, int tid, float c0, float c1,
                                               float c3, float c5, float bias, uint32_t *L) {
-    constexpr int R = kR;
-    static_assert(NR == R || NR == 2 * R, "one or two chunks");
+    constexpr int R = kR, ND = Reduce2Geom<B>::ND, kPitch = kReduce2Pitch;
+    static_assert(NR == R || NR == kReduce2TileRows, "one or two chunks");
     uint32_t r5[5], odd[R], even[R];
 #pragma unroll
     for (int k = 0; k < 5; ++k) r5[k] = load_row(2 * (y0 - 3 + k) + 1);
@@ -511,21 +257,19 @@ __device__ __forceinline__ void reduce2_vpass(const LoadRow &load_row, int y0, i
                                   tap7(c0, c1, c3, c5, bias, e.y, m1.y, p1.y, m3.y, p3.y, m5.y, p5.y),
                                   tap7(c0, c1, c3, c5, bias, e.z, m1.z, p1.z, m3.z, p3.z, m5.z, p5.z),
                                   tap7(c0, c1, c3, c5, bias, e.w, m1.w, p1.w, m3.w, p3.w, m5.w, p5.w));
-        if (ND >= kThreads || tid < ND) L[u * kPitch + tid] = d;
+        if (tid < ND) L[u * kPitch + tid] = d;  // ND <= 256 lanes hold a row's dwords
     }
 }
 
-// The one-pass tile (the shipped body): the geometry, arithmetic and LDS bytes of
-// reduce2_tile at R = 12 with register prefetch, but the tile's 24 rows go through one
-// load burst, one vertical pass, one barrier and one horizontal pass.  The 2 * R * kPitch
-// dwords are one 24-row image; the kernel ends after its output stores, so no wait covers
-// a store.  A band of at most 12 rows (the last tile of a window, a short image) takes
-// the 12-row vertical pass.
-template <int B, int WIDE, int TIGHT>
+// One tile: its 24 rows go through one load burst, one vertical pass, one barrier and one
+// horizontal pass.  The LDS is one 24-row image of packed intermediate bytes; the kernel
+// ends after its output stores, so no wait covers a store.  A band of at most 12 rows (the
+// last tile of a window, a short image) takes the 12-row vertical pass.
+template <int B>
 __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, int strip, int band,
                                                 uint32_t *lds) {
-    using G = R2<B, WIDE, TIGHT>;
-    constexpr int kThreads = G::kThreads, kPitch = G::kPitch;
+    using G = Reduce2Geom<B>;
+    constexpr int kThreads = kReduce2Threads, kPitch = kReduce2Pitch;
     constexpr int TW = G::TW;
     const int tid = threadIdx.x;
     const int x0 = (a.s_base + strip) * TW;
@@ -534,7 +278,8 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
     const int base = (B * px0) & ~3;     // floor to a dword (two's complement)
     const int byte0 = base + 4 * tid;
     const bool vlane = tid < G::ND && byte0 >= 0 && byte0 + 4 <= row_bytes;
-    // raw buffer loads as in reduce2_tile: lanes outside the row read 0
+    // raw buffer loads: per-lane byte offset in voffset, row offset in soffset;
+    // lanes outside the row get an out-of-range voffset and read 0
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<u8 *>(a.in + img * a.in_img), 0, static_cast<int>(a.in_img), 0x00020000);
     const uint32_t voff = vlane ? static_cast<uint32_t>(byte0) : 0x80000000u;
@@ -542,6 +287,8 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
     const int y1 = min(y0 + a.band_rows, a.y_end);
     const int rows = y1 - y0;            // 1 .. 24
     const float c0 = a.c0, c1 = a.c1, c3 = a.c3, c5 = a.c5, bias = a.bias;
+    // strip pixels outside the image (COPY edge): LDS pixels [0, nl) copy pixel 0,
+    // [fr, fr_end] copy pixel w-1; filled after the vertical pass
     const int nl = px0 < 0 ? -px0 : 0;
     const int x_last = min(x0 + TW, a.x_end) - 1;
     const int fr = a.w - px0;                                   // LDS index of pixel w
@@ -553,8 +300,8 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
         return static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, r * row_bytes, 0));
     };
     // ---- vertical pass: all intermediate rows of the tile -> LDS (packed uchar) ----
-    if (rows > kR) reduce2_vpass<2 * kR, G::ND, kThreads, kPitch>(load_row, y0, tid, c0, c1, c3, c5, bias, lds);
-    else reduce2_vpass<kR, G::ND, kThreads, kPitch>(load_row, y0, tid, c0, c1, c3, c5, bias, lds);
+    if (rows > kR) reduce2_vpass<B, kReduce2TileRows>(load_row, y0, tid, c0, c1, c3, c5, bias, lds);
+    else reduce2_vpass<B, kR>(load_row, y0, tid, c0, c1, c3, c5, bias, lds);
     if (nl > 0 || nr > 0) {  // replicate the edge pixels (EXTEND_COPY) inside the LDS image
         __syncthreads();
         u8 *Lb = reinterpret_cast<u8 *>(lds);
@@ -570,40 +317,22 @@ __device__ __forceinline__ void reduce2_onepass(const Reduce2Args &a, int img, i
     }
     __syncthreads();
     // ---- horizontal pass: 2 K output pixels per item, lanes walk down item columns ----
-    reduce2_hwalk<B, WIDE, TIGHT>(a, img, lds, x0, y0, rows, c0, c1, c3, c5, bias);
+    reduce2_hwalk<B>(a, img, lds, x0, y0, rows, c0, c1, c3, c5, bias);
 }
 
 // The centre sampling convention's 2 x 2 reduce is k_reduce2m (k_reduce2m.hip); its
 // all-VALU predecessor k_reduce2c (r04, 1.84-1.88 ms per C2 step) was removed once the
 // matrix-core kernel beat it, its measurements are under profiles/r04/reduce2c/.
 
-// Variant bits (A/B in one process via MIPX_R2_VARIANT; default = best measured):
-// bit 0: R = 6 (else 12), bit 1: register prefetch of the next chunk,
-// bit 2: packed-FP32 vertical taps, bit 3: memory-only diagnostic (not exact),
-// bit 4: non-temporal loads, bit 5: non-temporal stores, bit 6: 256-thread
-// workgroups over strips twice as wide, bit 7: 512-thread workgroups over
-// strips four times as wide.  Measured in
-// profiles/r01/v7_variants_ab.log: the memory-only build is no faster than the
-// full one (the arithmetic is hidden), packed math and nt hints lose.
-// bit 9: the chunk-loop body reduce2_tile (the bits above select its build); without it
-// the one-pass body reduce2_onepass at this strip width, which is R = 12 with prefetch.
-template <int B, int VAR>
-__global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kThreads) 
-    k_reduce2x2(Reduce2Args a) {
-    constexpr int WIDE = (VAR & 128) ? 2 : (VAR & 64) ? 1 : 0;
-    constexpr int TIGHT = (VAR & 256) ? 1 : 0;
-    constexpr int kPitch = R2T<WIDE, TIGHT>::kPitch;
-    constexpr int R = (VAR & 1) ? 6 : 12;
-    constexpr bool PF = (VAR & 2) != 0;
-    constexpr bool PK = (VAR & 4) != 0;
-    constexpr bool MEM = (VAR & 8) != 0;
-    constexpr int LAUX = (VAR & 16) ? 2 : 0;  // bit 4: non-temporal loads (cache policy nt)
-    constexpr bool NTS = (VAR & 32) != 0;     // bit 5: non-temporal stores
-    __shared__ __attribute__((aligned(16))) uint32_t lds[2 * R * kPitch];
-    // One-pass body: a new tile is the youngest wave on its SIMD and would queue for issue behind
-    // the older waves' arithmetic; it runs above them through the tile decode and the first 17
-    // loads of its burst (reduce2_vpass lowers it again), so its rows are on their way early
-    if constexpr ((VAR & 512) == 0) __builtin_amdgcn_s_setprio(2);
+// ID is the build's recorded identity in profiles/ and in the benchmark, not a selector.
+template <int B, int ID>
+__global__ void __launch_bounds__(kReduce2Threads) k_reduce2x2(Reduce2Args a) {
+    static_assert(ID == 66, "k_reduce2x2<B, 66> is the one build");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kReduce2TileRows * kReduce2Pitch];
+    // A new tile is the youngest wave on its SIMD and would queue for issue behind the older
+    // waves' arithmetic; it runs above them through the tile decode and the first 17 loads of
+    // its burst (reduce2_vpass lowers it again), so its rows are on their way early
+    __builtin_amdgcn_s_setprio(2);
     const uint32_t t = a.remap ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
     // t -> (img, band, strip) by exact multiply-shift division: all uniform, so it stays on
     // the scalar unit (a plain / would go through the vector float reciprocal, and every
@@ -620,14 +349,8 @@ __global__ void __launch_bounds__(R2T<(VAR & 128) ? 2 : (VAR & 64) ? 1 : 0>::kTh
         img = static_cast<int>(udiv_by(rest, a.bands_mul, a.bands_sh));
         band = static_cast<int>(rest - static_cast<uint32_t>(img) * static_cast<uint32_t>(a.n_bands));
     }
-    if constexpr ((VAR & 512) != 0) {
-        reduce2_tile<B, R, PF, PK, MEM, LAUX, NTS, WIDE, TIGHT>(a, img, strip, band, lds);
-    } else {
-        static_assert(R == kR && PF && !PK && !MEM && LAUX == 0 && !NTS, "the one-pass body has one build");
-        reduce2_onepass<B, WIDE, TIGHT>(a, img, strip, band, lds);
-    }
+    reduce2_onepass<B>(a, img, strip, band, lds);
 }
-
 
 }  // namespace
 
@@ -782,36 +505,15 @@ bool reduce2_eligible(const u8 *in, int w, int h, int b, double hs, double vs) {
     return shape_ok;
 }
 
-// k_reduce2x2 build variant: 66, the one-pass body (shipped), and 66 | 512 = 578, the
-// chunk-loop body it replaced (the A/B arm of scripts/ab_r2_onepass.py, and the body that
-// honours MIPX_R2_BAND: setting that knob selects it).  The r01 / r02
-// A/B builds (strip widths, register prefetch, LDS row strides) are recorded under
-// profiles/r01 and profiles/r02 (scripts/ab_reduce.py, in git history, ran them).  r06's
-// cache-policy A/B compiled 66 | 16 / 32 / 48 (82 / 98 / 114: non-temporal loads / stores /
-// both, the LAUX / NTS parameters of reduce2_tile) as extra cases here: -15 % / +0.2 % /
-// -14 % (profiles/r06/c2_nt_ab.jsonl), so none is kept.
-constexpr int kR2Default = 66;  // wide strips, R = 12 + register prefetch: measured best (profiles/r01/v10_wide_ab.log)
-constexpr int kR2Loop = kR2Default | 512;
-int reduce2_variant() {
-    const char *eb = tune_env("MIPX_R2_BAND");
-    if (eb && *eb) return kR2Loop;  // only the chunk loop walks bands of other heights
-    const char *e = tune_env("MIPX_R2_VARIANT");
-    if (!e || !*e) return kR2Default;
-    const int v = std::atoi(e);
-    switch (v) {
-        case kR2Default:
-        case kR2Loop: return v;
-        default: return kR2Default;
-    }
-}
-
 int reduce2_launch(const u8 *in, u8 *out, int n, int w, int h, int b, hipStream_t st) {
     return reduce2_window_launch(in, out, n, w, h, b, 0, 0, out_size_reduce(w, 2.0), out_size_reduce(h, 2.0), st);
 }
 
 // Only the output region [x0, x1) x [y0, y1) is computed (rounded out to whole
 // strips and 12-row chunks); the rest of the full-size output is left as it was.
-// Every computed pixel is the same sum as in the full launch.
+// Every computed pixel is the same sum as in the full launch.  One workgroup per tile of
+// reduce2_launch_geom's strips x bands (reduce2_geom.h) and image; MIPX_R2_REMAP and
+// MIPX_R2_ORDER set the order the tile index walks them in.
 int reduce2_window_launch(const u8 *in, u8 *out, int n, int w, int h, int b, int x0, int y0, int x1, int y1,
                           hipStream_t st) {
     if (reduce_centre()) {  // k_reduce2m: both passes on the matrix cores
@@ -823,30 +525,22 @@ int reduce2_window_launch(const u8 *in, u8 *out, int n, int w, int h, int b, int
     }
     float c[4];
     if (!reduce2_taps(c)) return MIPX_EINVAL;
+    Reduce2Launch g;
+    if (!reduce2_launch_geom(w, h, b, x0, y0, x1, y1, &g)) return MIPX_EINVAL;
     Reduce2Args a{};
     a.in = in;
     a.out = out;
     a.w = w;
     a.h = h;
-    a.ow = out_size_reduce(w, 2.0);
-    a.oh = out_size_reduce(h, 2.0);
-    if (x0 < 0 || y0 < 0 || x1 > a.ow || y1 > a.oh || x0 >= x1 || y0 >= y1) return MIPX_EINVAL;
-    const int var = reduce2_variant();
-    const int wl = (var & 128) ? 2 : (var & 64) ? 1 : 0;
-    const int tw = b == 3 ? (wl == 2 ? R2<3, 2>::TW : wl == 1 ? R2<3, 1>::TW : R2<3>::TW)
-                          : (wl == 2 ? R2<4, 2>::TW : wl == 1 ? R2<4, 1>::TW : R2<4>::TW);
-    a.s_base = x0 / tw;
-    a.x_end = x1;
-    a.y_base = y0 / kR * kR;
-    a.y_end = y1;
-    a.n_strips = (x1 + tw - 1) / tw - a.s_base;
-    const int chunks = (y1 - a.y_base + kR - 1) / kR;
-    // rows per workgroup: 2 chunks of 12 (measured best, profiles/r01/geom_ab.log; MIPX_R2_BAND overrides)
-    const char *eb = tune_env("MIPX_R2_BAND");
-    const int cpb = (eb && *eb) ? std::max(1, std::atoi(eb)) : 2;
-    const int chunks_per_band = std::max(1, std::min(chunks, cpb));
-    a.band_rows = chunks_per_band * kR;
-    a.n_bands = (y1 - a.y_base + a.band_rows - 1) / a.band_rows;
+    a.ow = g.ow;
+    a.oh = g.oh;
+    a.s_base = g.s_base;
+    a.x_end = g.x_end;
+    a.y_base = g.y_base;
+    a.y_end = g.y_end;
+    a.n_strips = g.n_strips;
+    a.band_rows = g.band_rows;
+    a.n_bands = g.n_bands;
     a.in_img = img_bytes(w, h, b);
     a.out_img = img_bytes(a.ow, a.oh, b);
     a.c0 = c[0] / 4096.0f;
@@ -858,26 +552,14 @@ int reduce2_window_launch(const u8 *in, u8 *out, int n, int w, int h, int b, int
     a.remap = (er && *er) ? std::atoi(er) : 1;
     const char *eo = tune_env("MIPX_R2_ORDER");
     a.band_major = (eo && *eo) ? std::atoi(eo) : 0;
-    const long long tiles = static_cast<long long>(a.n_strips) * a.n_bands * n;
+    const long long tiles = g.tiles_per_image() * n;
     if (tiles > 0x7fffffffLL) return MIPX_EINVAL;  // also what the decode's divisions rely on
     udiv_magic(static_cast<uint32_t>(a.n_strips), &a.strips_mul, &a.strips_sh);
     udiv_magic(static_cast<uint32_t>(a.n_bands), &a.bands_mul, &a.bands_sh);
-    dim3 grid(static_cast<unsigned>(tiles));
-#define MIPX_R2(V)                                                                                      \
-    case V: {                                                                                           \
-        const dim3 blk(R2T<(V & 128) ? 2 : (V & 64) ? 1 : 0>::kThreads);                                                   \
-        if (b == 3) hipLaunchKernelGGL((k_reduce2x2<3, V>), grid, blk, 0, st, a);                       \
-        else hipLaunchKernelGGL((k_reduce2x2<4, V>), grid, blk, 0, st, a);                              \
-        break;                                                                                          \
-    }
-    switch (var) {
-        MIPX_R2(66)
-        MIPX_R2(578)
-        default: return MIPX_EINVAL;
-    }
-#undef MIPX_R2
+    const dim3 grid(static_cast<unsigned>(tiles)), blk(kReduce2Threads);
+    if (b == 3) hipLaunchKernelGGL((k_reduce2x2<3, 66>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((k_reduce2x2<4, 66>), grid, blk, 0, st, a);
     return launch_check("k_reduce2x2");
 }
-
 
 }  // namespace mipx

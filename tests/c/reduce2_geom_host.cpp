@@ -1,17 +1,20 @@
-// reduce2_geom_host.cpp — reduce2_tile_interior (csrc/reduce2_geom.h) against a brute-force walk
-// of the tile, on the host: no HIP, no GPU; includes the header only.
+// reduce2_geom_host.cpp — k_reduce2x2's geometry (csrc/reduce2_geom.h) on the host: no HIP, no
+// GPU; includes the header only.
 //
-// The launch geometry is restated from reduce2_window_launch (k_reduce.hip): strips of 160 (RGB) /
-// 120 (RGBA) output pixels from the strip that holds the window's x0, bands of 24 rows (12 when the
-// window has at most 12) from its y0 rounded down to 12.  The walk is restated from the one-pass
-// body: 256 lanes, lane t loads dword t of the strip's bytes from floor4(B (2 x0 - 5)) in rows
-// 2 y0 - 5 .. 2 (y0 + 23) + 5 (t < ND), then 240 lanes take an item column (4 / 2 pixels) and walk
-// 24 rows, 6 / 4 apart, reading intermediate pixels 2 x - 5 .. 2 (x + K - 1) + 5 and storing
-// K * B bytes at (y * ow + x) * B of the image's output.
+// The launch of a window (reduce2_launch_geom, what the launcher in k_reduce.hip fills the
+// kernel's arguments from) is checked against a table of launches worked out by hand from the
+// rules: strips of 160 (RGB) / 120 (RGBA) output pixels from the strip that holds the window's x0,
+// bands of 24 rows (12 when the window has at most 12) from its y0 rounded down to 12.
+// reduce2_tile_interior is checked against a brute-force walk of the tile, restated from the
+// kernel's body with the header's constants: 256 lanes, lane t loads dword t of the strip's
+// bytes from floor4(B (2 x0 - 5)) in rows 2 y0 - 5 .. 2 (y0 + 23) + 5 (t < ND), then 240 lanes take
+// an item column (4 / 2 pixels) and walk 24 rows, 6 / 4 apart, reading intermediate pixels
+// 2 x - 5 .. 2 (x + K - 1) + 5 and storing K * B bytes at (y * ow + x) * B of the image's output.
 //
-//   (no argument)  enumerate shapes and windows; for every tile the predicate must equal "the walk
-//                  leaves the image, the window or the store alignment nowhere".  Prints the number
-//                  of tiles of each kind and "ok"; exits 1 at the first difference.
+//   (no argument)  the launch table, then enumerate shapes and windows; for every tile the
+//                  predicate must equal "the walk leaves the image, the window or the store
+//                  alignment nowhere".  Prints the number of tiles of each kind and "ok"; exits 1
+//                  at the first difference.
 //   count W H B    the interior tiles per image of the full W x H x B launch
 #include <cstdint>
 #include <cstdio>
@@ -26,32 +29,70 @@ using namespace mipx;
 
 namespace {
 
-struct Launch {
-    int w, h, b, ow, oh, tw, s_base, y_base, x_end, y_end, n_strips, n_bands, band_rows;
+// the header's launch of a window, with the image it belongs to
+struct Launch : Reduce2Launch {
+    int w, h, b, tw;
 };
 
-bool make_launch(int w, int h, int b, int x0, int y0, int x1, int y1, Launch *l) {
-    l->w = w, l->h = h, l->b = b;
-    l->ow = (w + 1) / 2, l->oh = (h + 1) / 2;  // VIPS_ROUND(in / 2)
-    if (x0 < 0 || y0 < 0 || x1 > l->ow || y1 > l->oh || x0 >= x1 || y0 >= y1) return false;
-    l->tw = b == 3 ? 160 : 120;
-    l->s_base = x0 / l->tw;
-    l->x_end = x1;
-    l->y_base = y0 / 12 * 12;
-    l->y_end = y1;
-    l->n_strips = (x1 + l->tw - 1) / l->tw - l->s_base;
-    const int chunks = (y1 - l->y_base + 11) / 12;
-    l->band_rows = (chunks < 2 ? chunks : 2) * 12;
-    l->n_bands = (y1 - l->y_base + l->band_rows - 1) / l->band_rows;
+bool launch_of(int w, int h, int b, int x0, int y0, int x1, int y1, Launch *l) {
+    l->w = w, l->h = h, l->b = b, l->tw = reduce2_strip_width(b);
+    return reduce2_launch_geom(w, h, b, x0, y0, x1, y1, l);
+}
+
+// Launches worked out by hand from the rules at the top; the output is (w + 1) / 2 x (h + 1) / 2.
+// Window {-1, ..}: the full image.
+struct Expect {
+    int w, h, b, x0, y0, x1, y1;
+    int s_base, y_base, n_strips, n_bands, band_rows;
+};
+constexpr Expect kLaunches[] = {
+    {3840, 2160, 3, -1, 0, 0, 0, /**/ 0, 0, 12, 45, 24},  // C2: 1920 / 160 strips, 1080 / 24 bands
+    {3840, 2160, 4, -1, 0, 0, 0, /**/ 0, 0, 16, 45, 24},  // 1920 / 120
+    {644, 98, 3, 0, 12, 322, 30, /**/ 0, 12, 3, 1, 24},   // 18 rows from a multiple of 12: one band of 2 chunks
+    {644, 98, 3, 150, 0, 170, 49, /**/ 0, 0, 2, 3, 24},   // columns 150 .. 169 lie in strips 0 and 1 of 160
+    {644, 98, 4, 150, 0, 170, 49, /**/ 1, 0, 1, 3, 24},   // and in strip 1 of 120 alone
+    {40, 24, 3, -1, 0, 0, 0, /**/ 0, 0, 1, 1, 12},        // 12 output rows: one chunk
+    {40, 26, 3, -1, 0, 0, 0, /**/ 0, 0, 1, 1, 24},        // 13 rows: two chunks
+    {8, 8, 4, -1, 0, 0, 0, /**/ 0, 0, 1, 1, 12},
+};
+
+bool check_table() {
+    for (const Expect &e : kLaunches) {
+        const int ow = (e.w + 1) / 2, oh = (e.h + 1) / 2;
+        const bool full = e.x0 < 0;
+        const int x0 = full ? 0 : e.x0, y0 = full ? 0 : e.y0, x1 = full ? ow : e.x1, y1 = full ? oh : e.y1;
+        Reduce2Launch l;
+        const bool ok = reduce2_launch_geom(e.w, e.h, e.b, x0, y0, x1, y1, &l);
+        if (!ok || l.ow != ow || l.oh != oh || l.s_base != e.s_base || l.y_base != e.y_base || l.x_end != x1 ||
+            l.y_end != y1 || l.n_strips != e.n_strips || l.n_bands != e.n_bands || l.band_rows != e.band_rows ||
+            l.tiles_per_image() != static_cast<long long>(e.n_strips) * e.n_bands) {
+            std::printf("launch %d x %d x %d window %d %d %d %d: ok %d, out %d x %d, s_base %d y_base %d x_end %d "
+                        "y_end %d, %d strips x %d bands of %d rows\n",
+                        e.w, e.h, e.b, x0, y0, x1, y1, ok, l.ow, l.oh, l.s_base, l.y_base, l.x_end, l.y_end,
+                        l.n_strips, l.n_bands, l.band_rows);
+            return false;
+        }
+    }
+    // 644 x 98 gives 322 x 49: empty windows, windows past the output, negative origins
+    const int bad[][4] = {{10, 0, 10, 49}, {11, 0, 10, 49}, {0, 20, 322, 20}, {0, 21, 322, 20}, {0, 0, 323, 49},
+                          {0, 0, 322, 50}, {-1, 0, 322, 49}, {0, -1, 322, 49}, {-160, -12, 322, 49}};
+    for (const auto &win : bad) {
+        Reduce2Launch l;
+        if (reduce2_launch_geom(644, 98, 3, win[0], win[1], win[2], win[3], &l)) {
+            std::printf("window %d %d %d %d of 322 x 49 was not rejected\n", win[0], win[1], win[2], win[3]);
+            return false;
+        }
+    }
     return true;
 }
 
 // would straight-line code with no edge handling stay inside the image, the window and the store alignment on
 // this tile?  misalign: low bits of the address of image 0's output; 3 images are walked
-bool walk_is_plain(const Launch &l, int x0, int y0, uint32_t misalign) {
-    if (l.band_rows != 24) return false;  // it walks 24 rows
-    const int B = l.b, K = B == 3 ? 4 : 2, ipr = l.tw / K, rpi = 256 / ipr;
-    const int npx = 2 * l.tw + 9, off0 = B == 3 ? 1 : 0, nd = (B * npx + off0 + 3) / 4;
+template <int B>
+bool walk_is_plain_b(const Launch &l, int x0, int y0, uint32_t misalign) {
+    using G = Reduce2Geom<B>;
+    if (l.band_rows != kReduce2TileRows) return false;  // it walks 24 rows
+    constexpr int K = G::K, ipr = G::IPR, rpi = G::RPI, nd = G::ND;
     const uint32_t al = B == 3 ? 4 : 8;
     const long long row_bytes = static_cast<long long>(l.w) * B;
     // loads: rows of the burst and of the 24-row pass, lanes t < nd
@@ -88,6 +129,10 @@ bool walk_is_plain(const Launch &l, int x0, int y0, uint32_t misalign) {
     return true;
 }
 
+bool walk_is_plain(const Launch &l, int x0, int y0, uint32_t misalign) {
+    return l.b == 3 ? walk_is_plain_b<3>(l, x0, y0, misalign) : walk_is_plain_b<4>(l, x0, y0, misalign);
+}
+
 long long n_interior, n_other;
 
 bool check_launch(const Launch &l) {
@@ -115,7 +160,7 @@ bool check_launch(const Launch &l) {
 
 int count_full(int w, int h, int b) {
     Launch l;
-    if (!make_launch(w, h, b, 0, 0, (w + 1) / 2, (h + 1) / 2, &l)) return -1;
+    if (!launch_of(w, h, b, 0, 0, (w + 1) / 2, (h + 1) / 2, &l)) return -1;
     int n = 0;
     for (int band = 0; band < l.n_bands; ++band)
         for (int strip = 0; strip < l.n_strips; ++strip)
@@ -131,6 +176,7 @@ int main(int argc, char **argv) {
         std::printf("%d\n", count_full(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4])));
         return 0;
     }
+    if (!check_table()) return 1;
     // w 8 .. 1400 by 11 and h 8 .. 220 by 7 (every residue mod 8), and every size around those at
     // which a tile turns interior: the right edge of strips 1, 2, ... and the last row of bands 1, 2, ...
     std::set<int> ws, hs;
@@ -154,7 +200,7 @@ int main(int argc, char **argv) {
                                           {5, 36, ow - tw / 2, oh - 13}};
                 for (const auto &win : windows) {
                     Launch l;
-                    if (!make_launch(w, h, b, win[0], win[1], win[2], win[3], &l)) continue;
+                    if (!launch_of(w, h, b, win[0], win[1], win[2], win[3], &l)) continue;
                     if (!check_launch(l)) return 1;
                     ++launches;
                 }

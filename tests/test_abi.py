@@ -167,9 +167,13 @@ def test_shipped_library_carries_no_unreachable_kernels_or_probes(tmp_path):
     assert "k_reduce2x2<3, 66>" in syms and "k_enlm<" in syms   # the listing does name kernels
     for k in ("k_rchain", "k_reduce2d", "k_reduce2w", "k_enlarge2"):
         assert k not in syms, k
+    # k_reduce2x2 has one build per band count (its A/B variants and their selectors went in r19)
+    one_build = {("3", "66"), ("4", "66")}
+    assert set(re.findall(r"k_reduce2x2<(\d+), (\d+)>", syms)) == one_build
     with open(ia.LIB_PATH, "rb") as f:
         blob = f.read()
-    for knob in (b"MIPX_ENLM_DBG", b"MIPX_BCOL_DBG", b"MIPX_CHAIN", b"MIPX_R2D", b"MIPX_R2_WALK", b"MIPX_ENLARGE2"):
+    for knob in (b"MIPX_ENLM_DBG", b"MIPX_BCOL_DBG", b"MIPX_CHAIN", b"MIPX_R2D", b"MIPX_R2_WALK", b"MIPX_ENLARGE2",
+                 b"MIPX_R2_VARIANT", b"MIPX_R2_BAND"):
         assert knob not in blob, knob
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     if os.path.exists(objdump):  # nor in the device code objects
@@ -180,6 +184,7 @@ def test_shipped_library_carries_no_unreachable_kernels_or_probes(tmp_path):
                        for p in tmp_path.iterdir() if "gfx950" in p.name)
         assert "k_enlm" in kern and "k_reduce2m" in kern
         assert not any(k in kern for k in ("k_rchain", "k_reduce2d", "k_reduce2w", "k_enlarge2"))
+        assert set(re.findall(r"k_reduce2x2<(\d+), (\d+)>", kern)) == one_build
 
 
 def test_build_id_is_the_hash_of_these_sources():

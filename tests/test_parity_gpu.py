@@ -74,9 +74,9 @@ def test_reduce_unaligned_batches(gpu, oracle, rng, h, w, b, hs, vs):
 
 @pytest.mark.parametrize("band", ["", "1", "16"])
 def test_reduce2x2_variants_exact(gpu, oracle, rng, convention, band, monkeypatch):
-    """The fused 2x2 kernels (corner: k_reduce2x2 variant 66, the r01/r02 A/B builds are
-    recorded under profiles/ and no longer compiled; centre: k_reduce2m, both passes on
-    the matrix cores, at its default band and at 1 / 16 steps per band) are bit-exact,
+    """The fused 2x2 kernels (corner: k_reduce2x2, which has one build; centre: k_reduce2m,
+    both passes on the matrix cores, at its default band and at 1 / 16 steps per band, the
+    variants of this test's name) are bit-exact,
     including strips that end at the image edge, images shorter than a band and the
     smallest eligible sizes."""
     monkeypatch.setenv("MIPX_R2M_BAND", band)

@@ -1,6 +1,8 @@
-"""Which k_reduce2x2 tiles touch no edge (csrc/reduce2_geom.h) on the host, no GPU.
-tests/c/reduce2_geom_host.cpp includes the header only and restates the launch geometry and the
-one-pass tile's walk; over w 8..1400 (every residue mod 8), h 8..220, RGB and RGBA, the full image
+"""k_reduce2x2's launch geometry, and which of its tiles touch no edge (csrc/reduce2_geom.h), on
+the host, no GPU.  tests/c/reduce2_geom_host.cpp includes the header only.  It first checks the
+launch the launcher takes from the header against a table of launches worked out by hand (C2's
+12 x 45 tiles, the demand windows and the one- and two-chunk shapes of the GPU tests, rejected
+windows).  Then it restates the tile's walk; over w 8..1400 (every residue mod 8), h 8..220, RGB and RGBA, the full image
 and demand windows whose y0 is a multiple of 12, and output bases on and off the store alignment, it
 demands for every tile that the predicate is true exactly when a brute-force walk of the tile finds
 no row or pixel index outside the image, no item past x_end and every store offset aligned.  The

@@ -1,4 +1,4 @@
-"""The one-pass k_reduce2x2 tile's horizontal pass (reduce2_hwalk, k_reduce.hip) against the
+"""The k_reduce2x2 tile's horizontal pass (reduce2_hwalk, k_reduce.hip) against the
 oracle, byte for byte, at the corner sampling convention.
 
 A lane takes one item column (4 pixels RGB, 2 RGBA) and walks down it 6 / 4 rows at a time
@@ -63,14 +63,8 @@ def _batch(oracle, w, h, b):
     return _batches[key]
 
 
-def _default_variant(monkeypatch):
-    monkeypatch.delenv("MIPX_R2_BAND", raising=False)
-    monkeypatch.delenv("MIPX_R2_VARIANT", raising=False)
-
-
 @pytest.mark.parametrize("b,w,h", CASES, ids=[f"{w}x{h}x{b}" for b, w, h in CASES])
-def test_hwalk_exact(gpu, oracle, corner, monkeypatch, b, w, h):
-    _default_variant(monkeypatch)
+def test_hwalk_exact(gpu, oracle, corner, b, w, h):
     for kind, imgs, want in _batch(oracle, w, h, b):
         got = gpu.run_op("reduce", imgs, hshrink=2.0, vshrink=2.0)
         assert got.shape == want.shape, (kind, got.shape, want.shape)
@@ -82,7 +76,7 @@ def test_hwalk_exact(gpu, oracle, corner, monkeypatch, b, w, h):
 # mipx::reduce2_window_launch(in, out, n, w, h, b, x0, y0, x1, y1, stream): the launcher the
 # demand-driven plans call; it is not part of the C ABI, so it is looked up by its C++ name
 _WINDOW_LAUNCH = "_ZN4mipx21reduce2_window_launchEPKhPhiiiiiiiiP12ihipStream_t"
-_STRIP = {3: 160, 4: 120}   # output pixels per strip (R2<B, 1>::TW)
+_STRIP = {3: 160, 4: 120}   # output pixels per strip (Reduce2Geom<B>::TW, reduce2_geom.h)
 _ITEM = {3: 4, 4: 2}        # output pixels per horizontal item: a window's right edge rounds to it
 
 # (x0, y0, x1, y1) in the 322 x 49 output of 644 x 98; None = the image's edge
@@ -95,14 +89,13 @@ WINDOWS = {
 
 @pytest.mark.parametrize("b", [3, 4])
 @pytest.mark.parametrize("window", list(WINDOWS))
-def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, monkeypatch, b, window):
+def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, b, window):
     """The launcher computes the window rounded out to whole strips on the left, to a multiple
     of 12 rows at the top and to a whole horizontal item (4 pixels RGB, 2 RGBA) on the right, and
     clips exactly at the bottom; every byte it computes equals the oracle and every other
     byte of the output keeps the poison, guard bands included."""
     from imaginary_amd._abi import check, sync_tuning
     from imaginary_amd.engine import GuardedBuffer
-    _default_variant(monkeypatch)
     w, h = 644, 98
     ow, oh = w // 2, h // 2
     x0, y0, x1, y1 = WINDOWS[window]

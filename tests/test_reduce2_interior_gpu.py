@@ -74,14 +74,8 @@ def _batch(oracle, w, h, b):
     return _batches[key]
 
 
-def _default_variant(monkeypatch):
-    for name in ("MIPX_R2_BAND", "MIPX_R2_VARIANT"):
-        monkeypatch.delenv(name, raising=False)
-
-
 @pytest.mark.parametrize("b,w,h", CASES, ids=[f"{w}x{h}x{b}" for b, w, h in CASES])
-def test_interior_and_its_neighbours_exact(gpu, oracle, corner, monkeypatch, b, w, h):
-    _default_variant(monkeypatch)
+def test_interior_and_its_neighbours_exact(gpu, oracle, corner, b, w, h):
     for kind, imgs, want in _batch(oracle, w, h, b):
         got = gpu.run_op("reduce", imgs, hshrink=2.0, vshrink=2.0)
         assert got.shape == want.shape, (kind, got.shape, want.shape)
@@ -92,7 +86,7 @@ def test_interior_and_its_neighbours_exact(gpu, oracle, corner, monkeypatch, b, 
 
 # mipx::reduce2_window_launch(in, out, n, w, h, b, x0, y0, x1, y1, stream), by its C++ name
 _WINDOW_LAUNCH = "_ZN4mipx21reduce2_window_launchEPKhPhiiiiiiiiP12ihipStream_t"
-_STRIP = {3: 160, 4: 120}   # output pixels per strip (R2<B, 1>::TW)
+_STRIP = {3: 160, 4: 120}   # output pixels per strip (Reduce2Geom<B>::TW, reduce2_geom.h)
 _ITEM = {3: 4, 4: 2}        # output pixels per horizontal item: a window's right edge rounds to it
 _SIZE = {3: (1288, 200), 4: (968, 200)}   # interior strips 1..3, interior bands 1..3 (rows 24..95)
 
@@ -109,14 +103,13 @@ WINDOWS = {
 
 @pytest.mark.parametrize("b", [3, 4])
 @pytest.mark.parametrize("window", list(WINDOWS))
-def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, monkeypatch, b, window):
+def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, b, window):
     """As the window test of tests/test_reduce2_hpass_gpu.py: the launcher computes the window
     rounded out to whole strips on the left, to a multiple of 12 rows at the top and to a whole
     item on the right, and clips exactly at the bottom; every byte it computes equals the oracle
     and every other byte of the output keeps the poison, guard bands included."""
     from imaginary_amd._abi import check, sync_tuning
     from imaginary_amd.engine import GuardedBuffer
-    _default_variant(monkeypatch)
     w, h = _SIZE[b]
     ow, oh = w // 2, h // 2
     x0, y0, x1, y1 = WINDOWS[window][b]

@@ -1,7 +1,6 @@
-"""k_reduce2x2's two bodies (k_reduce.hip) against the oracle, byte for byte, at the corner
-sampling convention: the one-pass tile (variant 66, the default: one load burst, one
-vertical pass over 24 rows, one barrier, one horizontal pass) and the chunk-loop tile it
-replaced (MIPX_R2_VARIANT=578).
+"""k_reduce2x2 (k_reduce.hip) against the oracle, byte for byte, at the corner sampling
+convention.  A tile is one load burst, one vertical pass over 24 rows, one barrier and one
+horizontal pass.
 
 The shapes are the places a 24-row, one-barrier tile can go wrong: a partial chunk,
 exactly one chunk (the 12-row vertical pass), 12 rows plus 1 (the 24-row pass with its
@@ -20,7 +19,6 @@ pytestmark = pytest.mark.gpu
 
 # input (w, h) -> output (w / 2, h / 2)
 SHAPES = [(8, 8), (40, 24), (40, 26), (40, 48), (40, 50), (40, 74), (324, 50), (644, 98)]
-VARIANTS = [None, "578"]
 N = 3
 
 
@@ -39,7 +37,7 @@ _batches = {}
 
 def _batch(oracle, w, h, b):
     """[(kind, images (3, h, w, b), oracle outputs)], computed once per shape and shared
-    by both variants; read-only."""
+    by the tests; read-only."""
     key = (w, h, b)
     if key not in _batches:
         r = np.random.default_rng(1000 * w + 10 * h + b)
@@ -60,38 +58,27 @@ def _batch(oracle, w, h, b):
     return _batches[key]
 
 
-def _select(monkeypatch, variant):
-    monkeypatch.delenv("MIPX_R2_BAND", raising=False)
-    if variant is None:
-        monkeypatch.delenv("MIPX_R2_VARIANT", raising=False)
-    else:
-        monkeypatch.setenv("MIPX_R2_VARIANT", variant)
-
-
-@pytest.mark.parametrize("variant", VARIANTS, ids=["default", "578"])
 @pytest.mark.parametrize("b", [3, 4])
 @pytest.mark.parametrize("w,h", SHAPES, ids=[f"{w}x{h}" for w, h in SHAPES])
-def test_onepass_and_chunk_loop_exact(gpu, oracle, corner, monkeypatch, w, h, b, variant):
-    _select(monkeypatch, variant)
+def test_onepass_exact(gpu, oracle, corner, w, h, b):
     for kind, imgs, want in _batch(oracle, w, h, b):
         got = gpu.run_op("reduce", imgs, hshrink=2.0, vshrink=2.0)
         assert got.shape == want.shape, (kind, got.shape, want.shape)
         d = np.argwhere(got != want)
-        assert len(d) == 0, (f"variant {variant} {w}x{h}x{b} {kind}: {len(d)} bytes differ, first at "
+        assert len(d) == 0, (f"{w}x{h}x{b} {kind}: {len(d)} bytes differ, first at "
                              f"{d[0].tolist()} got {got[tuple(d[0])]} want {want[tuple(d[0])]}")
 
 
 # mipx::reduce2_window_launch(in, out, n, w, h, b, x0, y0, x1, y1, stream): the launcher the
 # demand-driven plans call; it is not part of the C ABI, so it is looked up by its C++ name
 _WINDOW_LAUNCH = "_ZN4mipx21reduce2_window_launchEPKhPhiiiiiiiiP12ihipStream_t"
-_STRIP = {3: 160, 4: 120}   # output pixels per strip (R2<B, 1>::TW)
-_ITEM = {3: 4, 4: 2}        # output pixels per horizontal item (R2<B>::K)
+_STRIP = {3: 160, 4: 120}   # output pixels per strip (Reduce2Geom<B>::TW, reduce2_geom.h)
+_ITEM = {3: 4, 4: 2}        # output pixels per horizontal item (Reduce2Geom<B>::K)
 
 
-@pytest.mark.parametrize("variant", VARIANTS, ids=["default", "578"])
 @pytest.mark.parametrize("b", [3, 4])
 @pytest.mark.parametrize("window", ["rows", "cols"])
-def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, monkeypatch, b, window, variant):
+def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, b, window):
     """Rows [12, 30) and columns [150, 170) of the 322 x 49 output of 644 x 98.  The
     launcher computes the window rounded out to whole strips on the left, to a multiple of
     12 rows at the top (12 is one) and to a whole horizontal item (4 pixels RGB, 2 RGBA)
@@ -99,7 +86,6 @@ def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, monk
     oracle and every other byte of the output keeps the poison, guard bands included."""
     from imaginary_amd._abi import check, sync_tuning
     from imaginary_amd.engine import GuardedBuffer
-    _select(monkeypatch, variant)
     w, h = 644, 98
     ow, oh = w // 2, h // 2
     x0, y0, x1, y1 = (0, 12, ow, 30) if window == "rows" else (150, 0, 170, oh)
@@ -121,7 +107,7 @@ def test_demand_windows_exact_and_nothing_else_written(gpu, oracle, corner, monk
         dout.close()
     xl = x0 // _STRIP[b] * _STRIP[b]
     xr = min(-(-x1 // _ITEM[b]) * _ITEM[b], ow)
-    assert np.array_equal(got[:, y0:y1, xl:xr], want[:, y0:y1, xl:xr]), f"variant {variant} {window} x{b}"
+    assert np.array_equal(got[:, y0:y1, xl:xr], want[:, y0:y1, xl:xr]), f"{window} x{b}"
     outside = np.ones(got.shape, bool)
     outside[:, y0:y1, xl:xr] = False
-    assert np.all(got[outside] == FILL), f"variant {variant} {window} x{b}: wrote outside the window"
+    assert np.all(got[outside] == FILL), f"{window} x{b}: wrote outside the window"
