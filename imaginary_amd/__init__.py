@@ -10,7 +10,7 @@ from ._abi import (MIPX_OK, MIPX_EINVAL, MIPX_EUNSUPPORTED, MIPX_ENOMEM, MIPX_EN
 from .engine import (DeviceBuffer, Engine, GuardedBuffer, device_count, execute, fit_dimension,  # noqa: F401
                      guard_damage, guard_setting, guarded_calls, make_input, make_opts, plan_add_textmark, plan_chain,
                      plan_make, plan_textmark_geometry, reduce_sampling, run_op, set_guard, set_reduce_sampling,
-                     smartcrop_origins, synchronize, plan_set_ycc_input, ycc_bytes, ycc_to_rgb, YCC_444, YCC_420, YCC_422,
+                     smartcrop_origins, synchronize, plan_set_ycc_input, ycc_bytes, ycc_to_rgb, YCC_444, YCC_420, YCC_422, YCC_GREY,
                      plan_set_jpegc_output, jpegc_bytes, jpeg_qtables, rgb_to_jpegc,
                      plan_set_jpegd_input, plan_set_jpegd_input_scaled, jpegd_bytes, jpegd_to_rgb,
                      jpegd_to_rgb_scaled, plan_add_jpeg_roundtrip, jpeg_roundtrip,

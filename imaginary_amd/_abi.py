@@ -46,6 +46,7 @@ JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
 YCC_444 = 0   # planar JPEG input, coefficient input and output (MIPX_YCC_*): Cb, Cr at full size ...
 YCC_420 = 1   # ... or at ceil(w / 2) x ceil(h / 2)
 YCC_422 = 3   # ... or at ceil(w / 2) x h: an input layout only (MIPX_YCC_422; 2 is deliberately unused)
+YCC_GREY = 6  # one component, 1 band: coefficient input and output only (MIPX_YCC_GREY; 4, 5, 7 stay unknown)
 INTERPRETATION_SRGB = 22
 INTERPRETATION_BW = 26
 MAX_STEPS = 64

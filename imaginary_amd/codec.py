@@ -132,11 +132,16 @@ def decode_scale(w: int, h: int, shrink: int) -> int:
 YCC_444 = 0   # MIPX_YCC_444: Cb and Cr at full size
 YCC_420 = 1   # MIPX_YCC_420: Cb and Cr at ceil(w / 2) x ceil(h / 2)
 YCC_422 = 3   # MIPX_YCC_422: Cb and Cr at ceil(w / 2) x h (libjpeg's h2v1); an input layout only
+YCC_GREY = 6  # MIPX_YCC_GREY: one component, a 1-band image; coefficient input and output
 
 # The samplings (h, v) of Y, Cb, Cr that the input paths take, by layout.  4:2:2 is opt-in
 # (h2v1=True below): a caller that did not ask for it gets None for such a file, as before.
 _SAMPLINGS = {((1, 1), (1, 1), (1, 1)): YCC_444, ((2, 2), (1, 1), (1, 1)): YCC_420}
 _SAMPLINGS_H2V1 = {**_SAMPLINGS, ((2, 1), (1, 1), (1, 1)): YCC_422}
+# Opt-in as well (grey=True below).  A scan of one component is not interleaved, so its sampling
+# factors change nothing: 1 x 1 is what libjpeg writes by default and 2 x 2 what it writes when the
+# caller asked for 4:2:0 of a grey image, as encode() does below Q 90.
+_SAMPLING_GREY = {((1, 1),): YCC_GREY, ((2, 2),): YCC_GREY}
 
 
 def _sampling_geometry(w: int, h: int, samp):
@@ -253,6 +258,8 @@ def _huff_codes(table):
 def _jpegc_geometry(w: int, h: int, layout: int):
     """Per component (wb, hb, sampling factor), and the MCUs across and down."""
     ywb, yhb = (w + 7) // 8, (h + 7) // 8
+    if layout == YCC_GREY:        # one component: the scan is not interleaved, an MCU is a block
+        return [(ywb, yhb, 1)], ywb, yhb
     if layout == YCC_444:
         return [(ywb, yhb, 1)] * 3, ywb, yhb
     if layout != YCC_420:
@@ -283,10 +290,14 @@ def _padded_planes(coefs, w: int, h: int, layout: int):
     return planes, comps, mw, mh
 
 
-def jpeg_header(w: int, h: int, layout: int, quality: int, tables=None) -> bytes:
+def jpeg_header(w: int, h: int, layout: int, quality: int, tables=None, grey_sampling: int = 1) -> bytes:
     """SOI through SOS of the baseline JFIF file encode_jpeg_coefs writes: it depends on the
     size, the sampling (YCC_444 / YCC_420) and the quality only, not on the image, unless
-    `tables` (as HUFFMAN_TABLES: by DHT Tc/Th byte, (16 code counts, symbols)) replace Annex K's."""
+    `tables` (as HUFFMAN_TABLES: by DHT Tc/Th byte, (16 code counts, symbols)) replace Annex K's.
+    YCC_GREY writes what libjpeg writes for JCS_GRAYSCALE: one DQT (table 0), one component (id 1,
+    1 x 1, table 0), DHT DC 0 and AC 0 only, an SOS of one component.  grey_sampling: the factor the
+    one component declares both ways, 2 for the file libjpeg writes when its caller asked for 4:2:0
+    (the scan is the same: it is not interleaved)."""
     comps, _, _ = _jpegc_geometry(w, h, layout)
     lum, chrom = jpeg_qtables(quality)
     tables = HUFFMAN_TABLES if tables is None else tables
@@ -296,16 +307,26 @@ def jpeg_header(w: int, h: int, layout: int, quality: int, tables=None) -> bytes
 
     out = bytearray(b"\xff\xd8")
     out += seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
-    for i, t in enumerate((lum, chrom)):
+    for i, t in enumerate((lum, chrom)[:2 if len(comps) == 3 else 1]):
         out += seg(0xDB, bytes([i]) + bytes(t[k] for k in ZIGZAG))
-    sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3])
+    sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([len(comps)])
     for i, (_, _, s) in enumerate(comps):
+        if layout == YCC_GREY:
+            s = grey_sampling
         sof += bytes([i + 1, (s << 4) | s, 0 if i == 0 else 1])
     out += seg(0xC0, sof)
-    for tc in (0x00, 0x10, 0x01, 0x11):
+    for tc in _table_ids(layout):
         out += seg(0xC4, bytes([tc]) + bytes(tables[tc][0]) + bytes(tables[tc][1]))
-    out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    if layout == YCC_GREY:
+        out += seg(0xDA, bytes([1, 1, 0x00, 0, 63, 0]))
+    else:
+        out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
     return bytes(out)
+
+
+def _table_ids(layout: int):
+    """The DHT Tc/Th bytes of the tables a file of `layout` carries, in the order it writes them."""
+    return (0x00, 0x10) if layout == YCC_GREY else (0x00, 0x10, 0x01, 0x11)
 
 
 def _scan_symbols(coefs, w: int, h: int, layout: int):
@@ -347,9 +368,9 @@ def _scan_symbols(coefs, w: int, h: int, layout: int):
 
 def jpeg_symbol_counts(coefs, w: int, h: int, layout: int):
     """The scan's symbol counts by DHT Tc/Th byte, 256 each: Y counts into tables 0x00 and 0x10,
-    Cb and Cr together into 0x01 and 0x11 (what libjpeg's optimize_coding pass gathers).
-    ValueError as jpeg_scan."""
-    counts = {tc: [0] * 256 for tc in (0x00, 0x10, 0x01, 0x11)}
+    Cb and Cr together into 0x01 and 0x11 (what libjpeg's optimize_coding pass gathers); YCC_GREY
+    has tables 0x00 and 0x10 alone.  ValueError as jpeg_scan."""
+    counts = {tc: [0] * 256 for tc in _table_ids(layout)}
     for _, tc, sym, _ in _scan_symbols(coefs, w, h, layout):
         counts[tc][sym] += 1
     return counts
@@ -414,7 +435,7 @@ def jpeg_scan_bits(coefs, w: int, h: int, layout: int, tables=None):
     """(scan, bits): jpeg_scan's bytes, and the scan's length in bits before the last byte is
     padded and the 0xFF bytes are stuffed (what the engine's slot header reports)."""
     tables = HUFFMAN_TABLES if tables is None else tables
-    codes = {tc: _huff_codes(tables[tc]) for tc in (0x00, 0x10, 0x01, 0x11)}
+    codes = {tc: _huff_codes(tables[tc]) for tc in _table_ids(layout)}
     acc, nbits, total = 0, 0, 0  # the bit buffer, as one growing integer per MCU row
     scan = bytearray()
 
@@ -459,15 +480,15 @@ def jpeg_scan(coefs, w: int, h: int, layout: int, tables=None) -> bytes:
     return jpeg_scan_bits(coefs, w, h, layout, tables)[0]
 
 
-def jpeg_from_scan(scan, w: int, h: int, layout: int, quality: int, tables=None) -> bytes:
+def jpeg_from_scan(scan, w: int, h: int, layout: int, quality: int, tables=None, grey_sampling: int = 1) -> bytes:
     """The file: jpeg_header, the scan (jpeg_scan, or the bytes of an engine slot), EOI; `tables`
     are the ones the scan was coded with, None for Annex K's."""
-    return jpeg_header(w, h, layout, quality, tables) + bytes(scan) + b"\xff\xd9"
+    return jpeg_header(w, h, layout, quality, tables, grey_sampling) + bytes(scan) + b"\xff\xd9"
 
 
-def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int, tables=None) -> bytes:
+def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int, tables=None, grey_sampling: int = 1) -> bytes:
     """A baseline JFIF file from the engine's quantised coefficients (MIPX_OP_JPEGC), made at
-    `quality` in `layout` (YCC_444 / YCC_420).  Stand-in for libjpeg's jpeg_write_coefficients:
+    `quality` in `layout` (YCC_444 / YCC_420, or YCC_GREY: Y's blocks alone).  Stand-in for libjpeg's jpeg_write_coefficients:
     jpeg_from_scan of jpeg_scan.  tables: None for Annex K's, "optimal" for the ones libjpeg's
     optimize_coding makes of the image (jpeg_optimal_table of jpeg_symbol_counts), or a dict as
     jpeg_header takes."""
@@ -475,7 +496,7 @@ def encode_jpeg_coefs(coefs, w: int, h: int, layout: int, quality: int, tables=N
         if tables != "optimal":
             raise ValueError(f"tables {tables!r}")
         tables = {tc: jpeg_optimal_table(f) for tc, f in jpeg_symbol_counts(coefs, w, h, layout).items()}
-    return jpeg_from_scan(jpeg_scan(coefs, w, h, layout, tables), w, h, layout, quality, tables)
+    return jpeg_from_scan(jpeg_scan(coefs, w, h, layout, tables), w, h, layout, quality, tables, grey_sampling)
 
 
 # ---- quantised coefficients from a JPEG (the engine's MIPX_OP_JPEGD input) -----------------
@@ -498,12 +519,13 @@ def _huff_lookup(counts, symbols):
     return lut.tolist()
 
 
-def _jpeg_segments(buf: bytes, dht=None, span=None):
+def _jpeg_segments(buf: bytes, dht=None, span=None, grey=False):
     """What decode_jpeg_coefs needs of a file's headers, or None for a file it does not take:
     (w, h, components [(id, h, v, tq, td, ta)], tables {tq: 64 natural-order values}, Huffman
     lookups {Tc/Th byte: lookup}, restart interval, the entropy-coded intervals).  dht: a dict
     that takes the Huffman tables as the file has them, {Tc/Th byte: (16 counts, symbols)}.
-    span: a list that takes the offsets in buf of the scan's first byte and of its closing FF D9."""
+    span: a list that takes the offsets in buf of the scan's first byte and of its closing FF D9.
+    grey: take one-component files too (SOF and SOS of one component, a non-interleaved scan)."""
     import re
     if buf[:2] != b"\xff\xd8":
         return None
@@ -548,10 +570,12 @@ def _jpeg_segments(buf: bytes, dht=None, span=None):
                     dht[body[0]] = (bytes(body[1:17]), bytes(body[17:17 + cnt]))
                 body = body[17 + cnt:]
         elif m in (0xC0, 0xC1):                         # baseline, extended sequential; Huffman
-            if frame is not None or len(body) < 6 or body[0] != 8 or body[5] != 3 or len(body) != 6 + 9:
+            if frame is not None or len(body) < 6 or body[0] != 8 or body[5] not in ((3, 1) if grey else (3,)) \
+                    or len(body) != 6 + 3 * body[5]:
                 return None
             frame = (int.from_bytes(body[3:5], "big"), int.from_bytes(body[1:3], "big"),
-                     [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(3)])
+                     [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i])
+                      for i in range(body[5])])
         elif m == 0xDD:
             if len(body) != 2:
                 return None
@@ -561,8 +585,9 @@ def _jpeg_segments(buf: bytes, dht=None, span=None):
         elif 0xC0 <= m <= 0xCF or m in (0xDC, 0xD8, 0xD9):   # progressive, lossless, arithmetic, DNL, ...
             return None
     w, h, comps = frame if frame is not None else (0, 0, [])
-    if w <= 0 or h <= 0 or len(body) != 10 or body[0] != 3 or bytes(body[7:10]) != b"\x00\x3f\x00":
-        return None                                          # one interleaved scan of the whole spectrum
+    nc = len(comps)
+    if w <= 0 or h <= 0 or len(body) != 4 + 2 * nc or body[0] != nc or bytes(body[-3:]) != b"\x00\x3f\x00":
+        return None                                          # one scan of every component and the whole spectrum
     full = []
     for i, (cid, ch, cv, tq) in enumerate(comps):
         if body[1 + 2 * i] != cid or tq not in qt:
@@ -594,7 +619,7 @@ def _jpeg_segments(buf: bytes, dht=None, span=None):
     return w, h, full, qt, huff, restart, parts
 
 
-def decode_jpeg_coefs(buf: bytes, h2v1: bool = False):
+def decode_jpeg_coefs(buf: bytes, h2v1: bool = False, grey: bool = False):
     """A JPEG's quantised DCT coefficients as its entropy decoder has them, packed for the
     engine's MIPX_OP_JPEGD step: (payload, layout) with payload a 1-D uint8 array of the file's
     quantisation tables (Y, Cb, Cr: 64 little-endian uint16 each, natural order) and then the
@@ -607,15 +632,22 @@ def decode_jpeg_coefs(buf: bytes, h2v1: bool = False):
     h2v1=True takes 4:2:2 files too (sampling 2x1, 1x1, 1x1; layout YCC_422): chroma is
     ceil(ceil(w / 2) / 8) blocks across and ceil(h / 8) down, the MCU is Y left, Y right, Cb, Cr.
 
+    grey=True takes one-component files too (sampling 1x1, one scan; layout YCC_GREY): the header
+    keeps its 384 bytes, Y's table and zeros behind it, and the coefficients are Y's blocks alone.
+    The scan is not interleaved: an MCU is one block, so a restart interval counts blocks.
+
     Stand-in for libjpeg's jpeg_read_coefficients: a pure-Python Huffman decoder (any tables,
     restart intervals) that looks codes up by the next 16 bits of the stream."""
     try:
-        seg = _jpeg_segments(bytes(buf))
+        seg = _jpeg_segments(bytes(buf), grey=grey)
         if seg is None:
             return None
         w, h, comps, qt, huff, restart, parts = seg
         samp = tuple((c[1], c[2]) for c in comps)
         layout = (_SAMPLINGS_H2V1 if h2v1 else _SAMPLINGS).get(samp)
+        if layout is None and grey:
+            layout = _SAMPLING_GREY.get(samp)
+            samp = ((1, 1),)   # whatever it declares, the one component's blocks are the image's
         if layout is None:
             return None
         geo, mw, mh = _sampling_geometry(w, h, samp)
@@ -693,7 +725,8 @@ def decode_jpeg_coefs(buf: bytes, h2v1: bool = False):
             if a.size and (a.min() < -32768 or a.max() > 32767):
                 return None
             body.append(a.astype("<i2").ravel())
-        head = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel()
+        head = np.zeros(JPEGD_HEADER_BYTES // 2, "<u2")
+        head[:64 * len(comps)] = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel()
         return np.concatenate([head.view(np.uint8), np.concatenate(body).view(np.uint8)]), layout
     except Exception:  # noqa: BLE001 - whatever this decoder cannot read, the RGB decode reports
         return None
@@ -704,7 +737,7 @@ JPEGH_HEADER_BYTES = 1504   # MIPX_JPEGH_HEADER_BYTES
 JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD = 0, 1, 2   # MIPX_JPEGH_*
 
 
-def jpeg_huff_slot(buf: bytes, restart: bool = False, h2v1: bool = False):
+def jpeg_huff_slot(buf: bytes, restart: bool = False, h2v1: bool = False, grey: bool = False):
     """A JPEG's entropy-coded scan as the file has it, packed for the engine's entropy decoder
     (MIPX_JPEGH_HEADER_BYTES in include/mipx.h): (slot, layout) with slot a 1-D uint8 array of
     the scan's length, the quantisation tables of Y, Cb, Cr, the components' Huffman table
@@ -718,16 +751,24 @@ def jpeg_huff_slot(buf: bytes, restart: bool = False, h2v1: bool = False):
     the header at offset 4 (0 for a file without one) and the scan is the file's bytes between the
     SOS segment and FF D9 as they are, restart markers included; the engine checks the markers.
 
-    h2v1=True takes 4:2:2 files too, as decode_jpeg_coefs does (layout YCC_422)."""
+    h2v1=True takes 4:2:2 files too, as decode_jpeg_coefs does (layout YCC_422).
+
+    grey=True takes one-component files too, as decode_jpeg_coefs does (layout YCC_GREY): the header
+    keeps its size; Y's quantisation table stands at byte 16 with zeros behind it, byte 400 is Y's DC
+    table index and byte 403 its AC index (the other four are zero), every Huffman table the file
+    defines stands at its place, and the interval at offset 4 counts blocks."""
     try:
         buf = bytes(buf)
         dht, span = {}, []
-        seg = _jpeg_segments(buf, dht, span)
+        seg = _jpeg_segments(buf, dht, span, grey=grey)
         if seg is None:
             return None
         w, h, comps, qt, _, interval, parts = seg
         samp = tuple((c[1], c[2]) for c in comps)
         layout = (_SAMPLINGS_H2V1 if h2v1 else _SAMPLINGS).get(samp)
+        if layout is None and grey:
+            layout = _SAMPLING_GREY.get(samp)
+            samp = ((1, 1),)
         if layout is None:
             return None
         if not restart and (interval != 0 or len(parts) != 1):
@@ -743,8 +784,9 @@ def jpeg_huff_slot(buf: bytes, restart: bool = False, h2v1: bool = False):
         slot[0:4] = np.frombuffer(len(scan).to_bytes(4, "little"), np.uint8)
         if restart:
             slot[4:8] = np.frombuffer(interval.to_bytes(4, "little"), np.uint8)
-        slot[16:400] = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel().view(np.uint8)
-        slot[400:406] = [c[4] for c in comps] + [c[5] & 15 for c in comps]
+        slot[16:16 + 128 * len(comps)] = np.array([qt[c[3]] for c in comps], dtype="<u2").ravel().view(np.uint8)
+        for i, c in enumerate(comps):
+            slot[400 + i], slot[403 + i] = c[4], c[5] & 15
         for i, key in enumerate((0x00, 0x01, 0x10, 0x11)):
             if key in dht:
                 counts, symbols = dht[key]

@@ -66,15 +66,43 @@ __device__ __forceinline__ void put4(int16_t *s, const int v[4]) {
     *reinterpret_cast<uint2 *>(s) = make_uint2(pack16(v[0] - 128, v[1] - 128), pack16(v[2] - 128, v[3] - 128));
 }
 
+// 4 samples of one row of a 1-band image from column x0, byte k of the result; past w - 1 the last repeats
+__device__ __forceinline__ uint32_t load_grey4(const u8 *row, uint32_t x0, uint32_t w) {
+    uint32_t d = 0u;
+    if (x0 + 4u <= w) {
+        __builtin_memcpy(&d, row + x0, 4);  // any alignment: one global_load_dword
+        return d;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d |= static_cast<uint32_t>(row[min(x0 + k, w - 1u)]) << (8 * k);
+    return d;
+}
+
 // The pixels of strip (sx, sy) of a w x h image -> samples - 128 in the strip's LDS image, 256
 // threads.  The strip is 128 x 8 pixels in 4:4:4 (blocks 0..15 Y, 16..31 Cb, 32..47 Cr) and
 // 128 x 16 in 4:2:0 (blocks 0..31 two rows of Y, 32..39 Cb, 40..47 Cr).  ywb: real Y blocks
 // across; cwb, ch (4:2:0): real chroma blocks across, chroma rows.  A lane loads 4 pixels of one
-// row (4:4:4) or of two rows (4:2:0, one chroma sample pair) as 12-byte loads.
+// row (4:4:4) or of two rows (4:2:0, one chroma sample pair) as 12-byte loads.  In MIPX_YCC_GREY the
+// image has 1 band and the strip is 384 x 8 pixels, the 48 blocks of one block row in order: a lane
+// loads 4 samples three times, 96 lanes to a row.
 template <int LAYOUT>
 __device__ __forceinline__ void strip_samples(int16_t *blocks, const u8 *in, uint32_t w, uint32_t h, uint32_t ywb,
                                               uint32_t cwb, uint32_t ch, uint32_t sx, uint32_t sy) {
     const uint32_t tid = threadIdx.x;
+    if (LAYOUT == MIPX_YCC_GREY) {
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; ++i) {
+            const uint32_t t = tid + 256u * i, gr = t / 96u, gg = t - 96u * gr;  // row; group of 4 columns
+            const uint32_t gx0 = sx * 384u + 4u * gg;
+            if (gx0 < 8u * ywb) {
+                const uint32_t v = load_grey4(in + min(sy * 8u + gr, h - 1u) * w, gx0, w);
+                const int s4[4] = {static_cast<int>(v & 255u), static_cast<int>((v >> 8) & 255u),
+                                   static_cast<int>((v >> 16) & 255u), static_cast<int>(v >> 24)};
+                put4(blocks + (gg >> 1) * kBlockPitch + gr * 8u + (gg & 1u) * 4u, s4);
+            }
+        }
+        return;
+    }
     const uint32_t g = tid & 31u, r = tid >> 5;  // group of 4 columns; row (4:4:4) or row pair (4:2:0)
     const uint32_t x0 = sx * 128u + 4u * g;
     const uint32_t row_bytes = 3u * w;

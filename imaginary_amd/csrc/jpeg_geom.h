@@ -18,6 +18,12 @@ inline bool ycc_input_layout(int layout) {
     return layout == MIPX_YCC_444 || layout == MIPX_YCC_420 || layout == MIPX_YCC_422;
 }
 inline bool ycc_output_layout(int layout) { return layout == MIPX_YCC_444 || layout == MIPX_YCC_420; }
+// Those are the three-component ones: what MIPX_OP_YCC and MIPX_OP_JPEGRT take.  The steps that read
+// or write a file (MIPX_OP_JPEGD, MIPX_OP_JPEGH; MIPX_OP_JPEGC, MIPX_OP_JPEGE) take the one-component
+// layout too: its plane already is the image, of 1 band where the others make 3.
+inline bool jpeg_input_layout(int layout) { return ycc_input_layout(layout) || layout == MIPX_YCC_GREY; }
+inline bool jpeg_output_layout(int layout) { return ycc_output_layout(layout) || layout == MIPX_YCC_GREY; }
+inline int jpeg_layout_bands(int layout) { return layout == MIPX_YCC_GREY ? 1 : 3; }
 inline bool jpeg_quality_ok(int quality) { return quality >= 1 && quality <= 100; }
 // a decoding scale; where a caller takes 0 for 1 it passes jpeg_scale(s)
 inline bool jpeg_scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
@@ -40,7 +46,7 @@ struct JpegPlanes {
 
 struct JpegGeom {
     uint64_t hs = 0, vs = 0;          // Y's sampling factors; chroma's are 1
-    JpegComp y{}, c{};                // Y; Cb and Cr
+    JpegComp y{}, c{};                // Y; Cb and Cr (all zero in MIPX_YCC_GREY, which has none)
     uint64_t coef_off[3] = {};        // byte offset of each component's coefficients, 128 bytes per real block
     uint64_t plane_off[3] = {};       // ... and of its plane
     uint64_t coef_bytes = 0, plane_bytes = 0;  // per image
@@ -50,7 +56,14 @@ struct JpegGeom {
 
     // every field stays 0 for a size that is not positive or a layout that is none
     JpegGeom(int w, int h, int layout) {
-        if (w <= 0 || h <= 0 || !ycc_input_layout(layout)) return;
+        if (w <= 0 || h <= 0 || !jpeg_input_layout(layout)) return;
+        if (layout == MIPX_YCC_GREY) {  // one component: the non-interleaved scan, an MCU is a block
+            hs = vs = 1, y = comp(w, h);
+            coef_off[1] = coef_off[2] = coef_bytes = 128 * y.wb * y.hb;
+            plane_off[1] = plane_off[2] = plane_bytes = y.w * y.h;
+            mw = y.wb, mh = y.hb, per_mcu = 1, blocks = mw * mh;
+            return;
+        }
         hs = layout == MIPX_YCC_444 ? 1 : 2, vs = layout == MIPX_YCC_420 ? 2 : 1;
         y = comp(w, h), c = comp(ceil_div(w, hs), ceil_div(h, vs));
         coef_off[1] = 128 * y.wb * y.hb, coef_off[2] = coef_off[1] + 128 * c.wb * c.hb;
@@ -63,9 +76,15 @@ struct JpegGeom {
 
     // libjpeg's shrink-on-load (jdmaster.c): Y takes N = 8 / s; chroma takes twice that, up to 8, where
     // both of its ratios are 2 (4:2:0: three equal planes below full size); 4:2:2 keeps N and so its
-    // half-width chroma at every scale.  s = 1 gives the full-size planes above.
+    // half-width chroma at every scale.  s = 1 gives the full-size planes above.  Grey: its one plane.
     JpegPlanes planes(int s) const {
         JpegPlanes p{};
+        if (c.wb == 0) {
+            p.n[0] = p.n[1] = 8u / static_cast<uint32_t>(s);
+            p.w[0] = ceil_div(y.w, s), p.h[0] = ceil_div(y.h, s);
+            p.off[1] = p.off[2] = p.bytes = p.w[0] * p.h[0];
+            return p;
+        }
         const uint64_t both = hs < vs ? hs : vs;
         p.n[0] = 8u / static_cast<uint32_t>(s);
         p.n[1] = p.n[0] * both > 8 ? 8u : static_cast<uint32_t>(p.n[0] * both);
@@ -115,7 +134,8 @@ inline bool jpeg_blocks_fit_opt(uint64_t blocks) { return 64ull * blocks < 10000
 
 // ---- layout dispatch ----------------------------------------------------------------------
 // f(JpegLayout<L>()) with the layout as a compile-time constant; the output form instantiates nothing
-// for 4:2:2.  The caller has checked the layout.
+// for 4:2:2.  The caller has checked the layout.  Both have the one-component arm: a caller that does
+// not take it (k_jpegrt.hip) leaves that arm of its own empty.
 template <int L>
 struct JpegLayout {
     static constexpr int value = L;
@@ -123,12 +143,14 @@ struct JpegLayout {
 template <class F>
 inline void with_output_layout(int layout, F &&f) {
     if (layout == MIPX_YCC_420) f(JpegLayout<MIPX_YCC_420>());
+    else if (layout == MIPX_YCC_GREY) f(JpegLayout<MIPX_YCC_GREY>());
     else f(JpegLayout<MIPX_YCC_444>());
 }
 template <class F>
 inline void with_input_layout(int layout, F &&f) {
     if (layout == MIPX_YCC_420) f(JpegLayout<MIPX_YCC_420>());
     else if (layout == MIPX_YCC_422) f(JpegLayout<MIPX_YCC_422>());
+    else if (layout == MIPX_YCC_GREY) f(JpegLayout<MIPX_YCC_GREY>());
     else f(JpegLayout<MIPX_YCC_444>());
 }
 

@@ -41,9 +41,12 @@ __device__ __forceinline__ T block_scan(T v, T *wsum, T *total) {
     return base + inc - v;
 }
 
-// blocks of an MCU: Y Cb Cr; Y00 Y01 Y10 Y11 Cb Cr; 4:2:2's Y0 Y1 Cb Cr
+// blocks of an MCU: Y Cb Cr; Y00 Y01 Y10 Y11 Cb Cr; 4:2:2's Y0 Y1 Cb Cr; grey's one block (the scan of
+// one component is not interleaved)
 template <int LAYOUT>
-constexpr uint32_t per_mcu() { return LAYOUT == MIPX_YCC_444 ? 3u : LAYOUT == MIPX_YCC_422 ? 4u : 6u; }
+constexpr uint32_t per_mcu() {
+    return LAYOUT == MIPX_YCC_GREY ? 1u : LAYOUT == MIPX_YCC_444 ? 3u : LAYOUT == MIPX_YCC_422 ? 4u : 6u;
+}
 
 // Block s of the scan.  A component whose block grid is the MCU grid (chroma, and 4:4:4's Y) has
 // block m of that grid, in raster order, in MCU m.  The Y of a subsampled layout is `placed`: at
@@ -56,6 +59,11 @@ struct ScanBlock {
 };
 template <int LAYOUT>
 __device__ __forceinline__ ScanBlock scan_block(uint32_t s, uint32_t mw) {
+    if (LAYOUT == MIPX_YCC_GREY) {  // block s of Y's grid: its own MCU, never placed, never a dummy
+        ScanBlock g;
+        g.comp = 0u, g.m = s, g.j = 0u, g.placed = false, g.bx = g.by = 0u;
+        return g;
+    }
     constexpr uint32_t kPer = per_mcu<LAYOUT>(), kY = kPer - 2u;  // Y blocks of an MCU: 1, 2 across, 2 x 2
     ScanBlock b;
     b.m = s / kPer, b.j = s - kPer * b.m;

@@ -26,6 +26,13 @@
 // banks.  Every multiply has 24-bit operands (v_mad_i32_i24 / v_mul_u32_u24, full rate); the
 // division is a multiply by the host-built reciprocal of q (build_jpegc_recips).  Global
 // accesses are plain unaligned ones: rows, images and both pointers start on any byte.
+//
+// MIPX_YCC_GREY (PARITY_ASSUMPTIONS.md row 26): 1-band pixels in, Y's coefficients alone out: sample
+// - 128, the same edge rule, the luminance reciprocals.  Its strip is 384 x 8 pixels, the 48 blocks
+// of ONE block row, not three block rows of 128: a strip's pixel rows are then 384 contiguous bytes
+// (a wave and a half of 4-byte loads each) where three rows of 128 would be 24 pieces of 128, and
+// its 48 blocks are 6 KiB of contiguous output, so phases B to D run unchanged with all 384 tasks
+// busy wherever the image is 48 blocks across; only the last strip of a block row idles lanes.
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
@@ -58,6 +65,12 @@ constexpr uint32_t kNoBlock = 0xffffffffu;
 template <int LAYOUT>
 __device__ __forceinline__ uint32_t block_offset(const JpegcArgs &a, uint32_t sx, uint32_t sy, uint32_t blk,
                                                  uint32_t *chroma) {
+    if (LAYOUT == MIPX_YCC_GREY) {  // 48 blocks of block row sy
+        const uint32_t bx = sx * 48u + blk;
+        *chroma = 0u;
+        if (bx >= a.ywb) return kNoBlock;
+        return (sy * a.ywb + bx) * 128u;
+    }
     if (LAYOUT == MIPX_YCC_444) {
         const uint32_t comp = blk >> 4, bx = sx * 16u + (blk & 15u);
         *chroma = comp ? 64u : 0u;
@@ -138,7 +151,8 @@ __global__ void __launch_bounds__(256) k_jpegc(const JpegcArgs a) {
 
 int jpegc_launch(const u8 *d_in, u8 *d_out, int n, int w, int h, int layout, int quality, hipStream_t st) {
     const JpegGeom g(w, h, layout);
-    const long long in_img = static_cast<long long>(w) * h * 3;
+    const bool grey = layout == MIPX_YCC_GREY;
+    const long long in_img = static_cast<long long>(w) * h * jpeg_layout_bands(layout);
     const long long out_img = static_cast<long long>(g.coef_bytes);
     if (in_img > 0xffffffffLL || out_img > 0xffffffffLL) {  // byte offsets inside an image are 32-bit
         set_error("rgb to jpeg coefficients: image %dx%d too large (an image's bytes >= 2^32)", w, h);
@@ -156,7 +170,8 @@ int jpegc_launch(const u8 *d_in, u8 *d_out, int n, int w, int h, int layout, int
     a.ywb = static_cast<uint32_t>(g.y.wb), a.yhb = static_cast<uint32_t>(g.y.hb);
     a.cwb = static_cast<uint32_t>(g.c.wb), a.ch = static_cast<uint32_t>(g.c.h);
     a.cb_off = static_cast<uint32_t>(g.coef_off[1]), a.cr_off = static_cast<uint32_t>(g.coef_off[2]);
-    const long long gx = (static_cast<long long>(w) + 127) / 128, gy = static_cast<long long>(g.mh);  // a strip is a row of MCUs
+    // a strip is a row of MCUs, 128 pixels of it; grey's is 384 pixels of a block row
+    const long long gx = (static_cast<long long>(w) + (grey ? 383 : 127)) / (grey ? 384 : 128), gy = static_cast<long long>(g.mh);
     if (!grid_ok(gx * gy)) return MIPX_EUNSUPPORTED;
     a.gx = static_cast<uint32_t>(gx);
     const dim3 grid(static_cast<unsigned>(gx * gy), n);

@@ -148,7 +148,7 @@ int jpegd_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, 
     for (int c = 0; c < 2; ++c) {
         a.pw[c] = static_cast<uint32_t>(g.of(c).w), a.ph[c] = static_cast<uint32_t>(g.of(c).h);
         a.wb[c] = static_cast<uint32_t>(g.of(c).wb), a.hb[c] = static_cast<uint32_t>(g.of(c).hb);
-        a.runs[c] = (a.wb[c] + kRun - 1u) / kRun;
+        a.runs[c] = (a.wb[c] + kRun - 1u) / kRun;  // grey's chroma class: 0 runs, 0 groups
         a.groups[c] = a.runs[c] * a.hb[c];
         total += static_cast<long long>(a.runs[c]) * a.hb[c] * (c ? 2 : 1);
     }
@@ -198,7 +198,8 @@ int jpegd_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout, 
 // (pw = wb, ph = hb), so it is linear: a lane reads the DC terms of 4 consecutive blocks (2 bytes
 // each, 128 apart; nothing else of the block is touched) and stores 4 bytes, a wave 256.
 // Only the last block column of a plane stores fewer than N bytes, and rows past the plane's
-// height are not stored.
+// height are not stored.  MIPX_YCC_GREY: Y's workgroups alone, as in k_jpegd; the output is the
+// 1-band image of ceil(W / s) x ceil(H / s), at N = 1 the block grid's DC terms.
 namespace {
 
 struct JpegdsArgs {
@@ -360,6 +361,10 @@ int jpegds_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout,
     for (int c = 0; c < 2; ++c) {
         a.pw[c] = static_cast<uint32_t>(p.w[c]), a.nidct[c] = p.n[c];
         a.wb[c] = static_cast<uint32_t>(g.of(c).wb), a.hb[c] = static_cast<uint32_t>(g.of(c).hb);
+        if (a.wb[c] == 0u) {  // grey has no chroma: no workgroup is of this class, none reads runs[1]
+            a.runs[c] = a.groups[c] = 0u;
+            continue;
+        }
         if (a.nidct[c] == 1u) {  // linear over the block grid, which is the plane
             if (a.wb[c] != a.pw[c] || a.hb[c] != a.ph) return MIPX_EINVAL;
             const uint32_t per = 256u * kDcPerLane;

@@ -46,6 +46,11 @@
 // block in zigzag order, read 32 different banks.  Scan order is not memory order (4:2:0
 // interleaves two Y block rows and both chroma planes), but every block is one whole 128-byte line.
 // Coefficients and slots start on any byte: global accesses to them are plain unaligned ones.
+//
+// MIPX_YCC_GREY (PARITY_ASSUMPTIONS.md row 26): the scan of one component is not interleaved.  Block
+// s of the scan is block s of Y's grid in raster order, every block is real, the predictor is the
+// block before, and tables 0 code everything.  With optimised tables the histograms of DC 1 and AC 1
+// stay zero; see k_jpege_tables for what its two waves then do.
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
@@ -111,6 +116,11 @@ __device__ __forceinline__ int load_i16(const u8 *p) {
 template <int LAYOUT>
 __device__ __forceinline__ uint32_t block_src(const JpegeArgs &a, uint32_t s, bool *real, uint32_t *chroma,
                                               uint32_t *prev) {
+    if (LAYOUT == MIPX_YCC_GREY) {  // an MCU is a block; no dummy blocks
+        *real = true, *chroma = 0u;
+        *prev = s ? s - 1u : kNone;
+        return s * 128u;
+    }
     if (LAYOUT == MIPX_YCC_444) {  // Y Cb Cr per MCU; MCUs are the blocks in raster order
         const uint32_t m = s / 3u, c = s - 3u * m;
         *real = true, *chroma = c ? 1u : 0u;
@@ -333,6 +343,12 @@ __device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, i
 // then largest index); every entry of either tree then grows by one bit and joins c1's, which is
 // what the library's walk along its `others` chains does.  The waves run different numbers of merges
 // and meet again at the barriers behind them.
+// A table no symbol was counted into (MIPX_YCC_GREY's DC 1 and AC 1) has one live key, the reserved
+// point: its wave leaves the merge loop at the first test, no entry gets a size, lane 0 finds no
+// longest length and takes no code away, and the wave writes 272 zero bytes as the DHT and 256 zero
+// codes, which no block reads.  Zeros are "a table the file does not define" in a MIPX_OP_JPEGH slot.
+// So jpeg_gen_optimal_table's merges never run on an all-zero histogram, and the two idle waves only
+// keep the barriers' company.
 // PACKED: the slot's place is not known yet, so the DHTs go to the head of the image's histogram
 // (every wave has its counts in registers before the first barrier) for k_jpege_stuff to copy.
 template <bool PACKED>

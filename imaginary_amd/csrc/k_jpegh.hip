@@ -7,7 +7,10 @@
 // synchronise: the unstuffed stream is cut into subsequences of kJpeghSub bytes, one lane each, and
 // sequences of kJpeghSeq subsequences, one workgroup each.  The state a decoder needs at a bit is
 // (block index inside the MCU, zigzag index); an MCU is 3 blocks in 4:4:4, 6 in 4:2:0 and 4 in
-// 4:2:2 (Y left, Y right, Cb, Cr; the chroma grid is then the MCU grid).  Every dependency
+// 4:2:2 (Y left, Y right, Cb, Cr; the chroma grid is then the MCU grid), and the one block in
+// MIPX_YCC_GREY, whose scan is not interleaved (row 26): block s is block s of Y's grid, there are no
+// dummy blocks, a restart interval counts blocks, and one DC chain runs where the others have three
+// (JpeghArgs::comps; dc_sums and dc_offs keep their stride of 3).  Every dependency
 // between workgroups is a launch boundary on the stream; no kernel waits for another workgroup;
 // every loop has a bound.
 //   memset             the statuses, the per-image records, the payloads (zero coefficients)
@@ -106,6 +109,7 @@ struct JpeghArgs {
     uint32_t wblocks;              // the stride of dcdiff
     uint32_t ywb, yhb, mw;
     uint32_t cb_off, cr_off;       // byte offsets of Cb and Cr in the payload's coefficients
+    uint32_t comps;                // components of the scan: 3, or 1 (grey)
 };
 
 __device__ __forceinline__ uint32_t load_u32(const u8 *p) {
@@ -220,8 +224,8 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_prep(const JpeghArgs a) {
     if (tid < 4u) {
         int maxcode[17], valoff[17];
         if (!canonical(slot + kTablesOff + kTableBytes * tid, maxcode, valoff)) bad = true;
-    } else if (tid < 10u) {
-        if (slot[kSelOff + tid - 4u] > 1u) bad = true;
+    } else if (tid < 10u) {  // the table indices of the components the scan has: DC of 0 1 2, then AC
+        if ((tid - 4u) % 3u < a.comps && slot[kSelOff + tid - 4u] > 1u) bad = true;
     }
     const uint32_t count = (length + kChunk - 1u) / kChunk;
     const uint32_t *sums = a.chunk_sums + static_cast<size_t>(img) * a.chunks;
@@ -290,7 +294,10 @@ __device__ __forceinline__ void load_tables(const u8 *slot, Huff &H) {
     if (tid == 4u) {
         const uint32_t d[3] = {slot[kSelOff] & 1u, slot[kSelOff + 1u] & 1u, slot[kSelOff + 2u] & 1u};
         const uint32_t c[3] = {slot[kSelOff + 3u] & 1u, slot[kSelOff + 4u] & 1u, slot[kSelOff + 5u] & 1u};
-        if (LAYOUT == MIPX_YCC_444) {
+        if (LAYOUT == MIPX_YCC_GREY) {  // Y's alone: bytes 400 and 403
+            H.dcsel = d[0];
+            H.acsel = c[0];
+        } else if (LAYOUT == MIPX_YCC_444) {
             H.dcsel = d[0] | d[1] << 1 | d[2] << 2;
             H.acsel = c[0] | c[1] << 1 | c[2] << 2;
         } else if (LAYOUT == MIPX_YCC_422) {
@@ -603,8 +610,9 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_dcsum(const JpeghArgs a) {
     if (a.status[img] != MIPX_JPEGH_OK) return;
     const int d = cur < a.blocks ? a.dcdiff[static_cast<size_t>(img) * a.wblocks + cur] : 0;
     const uint32_t comp = scan_block<LAYOUT>(cur, 1u).comp;
+    constexpr uint32_t kComps = LAYOUT == MIPX_YCC_GREY ? 1u : 3u;
 #pragma unroll
-    for (uint32_t c = 0; c < 3u; ++c) {
+    for (uint32_t c = 0; c < kComps; ++c) {
         int total;  // 256 differences of 15 bits and a sign
         block_scan<int>(comp == c ? d : 0, wsum, &total);
         if (threadIdx.x == 0) a.dc_sums[(static_cast<size_t>(img) * a.tiles + tile) * 3u + c] = total;
@@ -618,7 +626,7 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_dcscan(const JpeghArgs a) {
     const uint32_t count = (a.blocks + kLanes - 1u) / kLanes;
     const int *sums = a.dc_sums + static_cast<size_t>(img) * a.tiles * 3u;
     long long *offs = a.dc_offs + static_cast<size_t>(img) * a.tiles * 3u;
-    for (uint32_t c = 0; c < 3u; ++c) {
+    for (uint32_t c = 0; c < a.comps; ++c) {  // grey's k_jpegh_dcsum writes component 0 alone
         long long carry = 0;
         for (uint32_t base = 0; base < count; base += kLanes) {
             const uint32_t i = base + tid;
@@ -650,8 +658,9 @@ __global__ void __launch_bounds__(kLanes) k_jpegh_dcwrite(const JpeghArgs a) {
     uint32_t comp = 0;
     const uint32_t dst = valid ? block_dst<LAYOUT>(a, cur, &comp) : kNone;
     long long dc = 0;
+    constexpr uint32_t kComps = LAYOUT == MIPX_YCC_GREY ? 1u : 3u;
 #pragma unroll
-    for (uint32_t c = 0; c < 3u; ++c) {
+    for (uint32_t c = 0; c < kComps; ++c) {
         int total;
         const int before = block_scan<int>(valid && comp == c ? d : 0, wsum, &total);
         if (comp == c) dc = a.dc_offs[(static_cast<size_t>(img) * a.tiles + tile) * 3u + c] + before + d;
@@ -832,6 +841,7 @@ int jpegh_launch(const u8 *d_slots, u8 *d_payloads, uint32_t *d_status, int n, i
     a.ywb = static_cast<uint32_t>(g.y.wb), a.yhb = static_cast<uint32_t>(g.y.hb), a.mw = static_cast<uint32_t>(g.mw);
     a.cb_off = static_cast<uint32_t>(g.coef_off[1]), a.cr_off = static_cast<uint32_t>(g.coef_off[2]);
     a.blocks = static_cast<uint32_t>(g.blocks), a.mcus = static_cast<uint32_t>(mcus);
+    a.comps = static_cast<uint32_t>(jpeg_layout_bands(layout));
     MIPX_HIP(hipMemsetAsync(d_status, 0, static_cast<size_t>(n) * 4, st));
     MIPX_HIP(hipMemsetAsync(work + W.info, 0, static_cast<size_t>(n) * sizeof(JpeghInfo), st));
     MIPX_HIP(hipMemsetAsync(d_payloads, 0, static_cast<size_t>(n) * (MIPX_JPEGD_HEADER_BYTES + static_cast<size_t>(a.cap)), st));

@@ -185,7 +185,9 @@ int jpegrt_launch(const u8 *d_in, u8 *d_planes, int n, int w, int h, int layout,
     if (!grid_ok(gx * gy)) return MIPX_EUNSUPPORTED;
     a.gx = static_cast<uint32_t>(gx);
     const dim3 grid(static_cast<unsigned>(gx * gy), n);
-    with_output_layout(layout, [&](auto L) { launch<L.value>(shrink, grid, st, a); });
+    with_output_layout(layout, [&](auto L) {  // the caller has refused grey: no round trip of one component is built
+        if constexpr (L.value != MIPX_YCC_GREY) launch<L.value>(shrink, grid, st, a);
+    });
     return launch_check("k_jpegrt");
 }
 

@@ -162,7 +162,7 @@ int mipx_op_ycc_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w
 
 int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                          int32_t quality, void *stream) {
-    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_output_layout(layout) || !jpeg_quality_ok(quality))
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !jpeg_output_layout(layout) || !jpeg_quality_ok(quality))
         return MIPX_EINVAL;
     return jpegc_launch(d_in, d_out, n, w, h, layout, quality, as_stream(stream));
 }
@@ -170,7 +170,7 @@ int mipx_op_rgb_to_jpegc(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
 // The checks the four entropy-coder calls share.
 static int jpege_check(const char *what, const void *d_in, const void *d_out, const void *d_work, int32_t n, int32_t w,
                        int32_t h, int32_t layout, bool optimise) {
-    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || !ycc_output_layout(layout)) return MIPX_EINVAL;
+    if (!d_in || !d_out || !d_work || !geom_ok(n, w, h, 3) || !jpeg_output_layout(layout)) return MIPX_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_work) & 15u) {
         set_error("%s: the workspace is not 16-byte aligned", what);
         return MIPX_EINVAL;
@@ -260,7 +260,7 @@ int mipx_op_rgb_to_jpeg_scan_packed(const uint8_t *d_in, uint8_t *d_out, int32_t
 // The checks the three entropy-decoder calls share; *work: the workspace.
 static int jpegh_check(const char *what, const void *d_slots, const void *d_out, const uint32_t *d_status, int32_t n,
                        int32_t w, int32_t h, int32_t layout, void *d_ws, size_t ws_bytes) {
-    if (!d_slots || !d_out || !d_status || !d_ws || !geom_ok(n, w, h, 3) || !ycc_input_layout(layout))
+    if (!d_slots || !d_out || !d_status || !d_ws || !geom_ok(n, w, h, 3) || !jpeg_input_layout(layout))
         return MIPX_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_ws) & 15u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
         set_error("%s: the workspace is not 16-byte aligned, or the statuses are not 4-byte aligned", what);
@@ -307,7 +307,7 @@ int mipx_op_jpegh_to_rgb(const uint8_t *d_slots, uint8_t *d_out, uint32_t *d_sta
 
 int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t w, int32_t h, int32_t layout,
                          void *d_ws, size_t ws_bytes, void *stream) {
-    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !ycc_input_layout(layout)) return MIPX_EINVAL;
+    if (!d_in || !d_out || !geom_ok(n, w, h, 3) || !jpeg_input_layout(layout)) return MIPX_EINVAL;
     // byte offsets inside an image are 32-bit in both kernels
     if (!jpeg_fits_32(JpegGeom(w, h, layout), w, h)) {
         set_error("jpeg coefficients to rgb: image %dx%d too large (an image's bytes >= 2^32)", w, h);
@@ -318,6 +318,8 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
                   op_workspace_bytes(MIPX_OP_JPEGD, n, w, h, 3, 0, 0));
         return MIPX_EINVAL;
     }
+    // grey: Y's plane is the 1-band image; nothing is upsampled or converted, the workspace stays idle
+    if (layout == MIPX_YCC_GREY) return jpegd_launch(d_in, d_out, n, w, h, layout, as_stream(stream));
     uint8_t *planes = static_cast<uint8_t *>(d_ws);
     const int e = jpegd_launch(d_in, planes, n, w, h, layout, as_stream(stream));
     if (e) return e;
@@ -327,7 +329,7 @@ int mipx_op_jpegd_to_rgb(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t
 int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, int32_t file_w, int32_t file_h,
                                 int32_t layout, int32_t shrink, void *d_ws, size_t ws_bytes, void *stream) {
     if (shrink == 1) return mipx_op_jpegd_to_rgb(d_in, d_out, n, file_w, file_h, layout, d_ws, ws_bytes, stream);
-    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || !ycc_input_layout(layout) || !jpeg_scale_ok(shrink))
+    if (!d_in || !d_out || !geom_ok(n, file_w, file_h, 3) || !jpeg_input_layout(layout) || !jpeg_scale_ok(shrink))
         return MIPX_EINVAL;
     const int ow = static_cast<int>((static_cast<long long>(file_w) + shrink - 1) / shrink);
     const int oh = static_cast<int>((static_cast<long long>(file_h) + shrink - 1) / shrink);
@@ -344,6 +346,8 @@ int mipx_op_jpegd_to_rgb_scaled(const uint8_t *d_in, uint8_t *d_out, int32_t n, 
     }
     // three ow x oh planes: no upsampling at these scales; but of a 4:2:2 file its planes at the decoded
     // size, whose chroma libjpeg replicates at 1 / 8 whatever its width
+    if (layout == MIPX_YCC_GREY)  // the one plane of ow x oh is the image
+        return jpegds_launch(d_in, d_out, n, file_w, file_h, layout, shrink, as_stream(stream));
     uint8_t *planes = static_cast<uint8_t *>(d_ws);
     const int e = jpegds_launch(d_in, planes, n, file_w, file_h, layout, shrink, as_stream(stream));
     if (e) return e;

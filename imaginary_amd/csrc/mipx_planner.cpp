@@ -631,16 +631,18 @@ extern "C" size_t mipx_jpegh_bytes(int32_t w, int32_t h, int32_t layout) {
 
 // the output slots: of the layouts a JPEG is written in
 extern "C" size_t mipx_jpeg_scan_bytes(int32_t w, int32_t h, int32_t layout) {
-    return mipx::ycc_output_layout(layout) ? behind_header(MIPX_JPEG_SCAN_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout)) : 0;
+    return mipx::jpeg_output_layout(layout) ? behind_header(MIPX_JPEG_SCAN_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout)) : 0;
 }
 
 extern "C" size_t mipx_jpeg_scan_opt_bytes(int32_t w, int32_t h, int32_t layout) {
-    return mipx::ycc_output_layout(layout) ? behind_header(MIPX_JPEG_SCAN_OPT_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout)) : 0;
+    return mipx::jpeg_output_layout(layout) ? behind_header(MIPX_JPEG_SCAN_OPT_HEADER_BYTES, mipx_jpegc_bytes(w, h, layout)) : 0;
 }
 
-// Every layout but 4:2:0 counts as 4:4:4, the input-only 4:2:2 too: the callers reject that one themselves.
+// 4:2:0 and grey count their own blocks; every other layout counts as 4:4:4, the input-only 4:2:2 too:
+// the callers reject that one themselves.
 bool mipx::jpeg_opt_in_range(int w, int h, int layout) {
-    return jpeg_blocks_fit_opt(JpegGeom(w, h, layout == MIPX_YCC_420 ? MIPX_YCC_420 : MIPX_YCC_444).blocks);
+    const bool own = layout == MIPX_YCC_420 || layout == MIPX_YCC_GREY;
+    return jpeg_blocks_fit_opt(JpegGeom(w, h, own ? layout : MIPX_YCC_444).blocks);
 }
 
 size_t mipx::plan_input_bytes(const mipx_plan *p) {
@@ -678,9 +680,13 @@ extern "C" int mipx_jpeg_qtables(int32_t quality, uint8_t lum[64], uint8_t chr[6
 // step behind the plan's last, a[] = {layout, quality, a2}.  a2 is MIPX_OP_JPEGRT's shrink (0 for 1),
 // which only that step checks, with the 32-bit limit of its two kernels; MIPX_OP_JPEGE's "optimised",
 // which brings the 10^9 rule; 0 for MIPX_OP_JPEGC.  makes: what the step makes of 3 bands.
+// MIPX_OP_JPEGC and MIPX_OP_JPEGE take MIPX_YCC_GREY, and that on 1 band: a layout goes with its band
+// count alone; the round trip does not take it.
 static int append_jpeg_step(mipx_plan *plan, const char *who, const char *makes, int32_t op, int32_t layout,
                             int32_t quality, int32_t a2) {
-    if (!plan_header_ok(plan) || !mipx::ycc_output_layout(layout)) return MIPX_EINVAL;
+    if (!plan_header_ok(plan)) return MIPX_EINVAL;
+    if (!(op == MIPX_OP_JPEGRT ? mipx::ycc_output_layout(layout) : mipx::jpeg_output_layout(layout))) return MIPX_EINVAL;
+    const int32_t bands = mipx::jpeg_layout_bands(layout);
     if (!mipx::jpeg_quality_ok(quality)) {
         mipx::set_error("%s: quality %d outside 1..100", who, quality);
         return MIPX_EINVAL;
@@ -689,9 +695,9 @@ static int append_jpeg_step(mipx_plan *plan, const char *who, const char *makes,
         mipx::set_error("%s: shrink %d is not 1, 2, 4 or 8", who, a2);
         return MIPX_EINVAL;
     }
-    if (plan->out_bands != 3 || plan->out_w <= 0 || plan->out_h <= 0) {
-        mipx::set_error("%s: the plan makes %dx%dx%d, %s of 3 bands", who, plan->out_w, plan->out_h, plan->out_bands,
-                        makes);
+    if (plan->out_bands != bands || plan->out_w <= 0 || plan->out_h <= 0) {
+        mipx::set_error("%s: the plan makes %dx%dx%d, %s of %d band%s", who, plan->out_w, plan->out_h, plan->out_bands,
+                        makes, bands, bands == 1 ? " in this layout" : "s");
         return MIPX_EINVAL;
     }
     if (op == MIPX_OP_JPEGRT &&
@@ -716,7 +722,7 @@ static int append_jpeg_step(mipx_plan *plan, const char *who, const char *makes,
     std::memset(&s, 0, sizeof(s));
     s.op = op;
     s.a[0] = layout, s.a[1] = quality, s.a[2] = a2;
-    s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = 3;
+    s.out_w = plan->out_w, s.out_h = plan->out_h, s.out_bands = bands;
     return MIPX_OK;
 }
 
@@ -748,13 +754,17 @@ extern "C" int mipx_plan_add_jpeg_roundtrip(mipx_plan *plan, int32_t layout, int
 // ---- JPEG input steps: MIPX_OP_YCC, MIPX_OP_JPEGD, MIPX_OP_JPEGH ------------------------------
 // What the setters of the three share: their checks and the zeroed step in front of the plan's first.
 // shrink 1: the full-size step; 2, 4, 8: the step that decodes the file_w x file_h file at that scale
-// (MIPX_OP_JPEGD, and MIPX_OP_JPEGH for the same step behind the entropy decoder; planes come at full size)
+// (MIPX_OP_JPEGD, and MIPX_OP_JPEGH for the same step behind the entropy decoder; planes come at full size).
+// MIPX_OP_JPEGD and MIPX_OP_JPEGH take MIPX_YCC_GREY, and that on a plan of 1 band, which their step then
+// makes; planes are three components' and do not.
 static int prepend_jpeg_step(mipx_plan *plan, const char *who, int32_t op, int32_t layout, int32_t shrink,
                              int32_t file_w, int32_t file_h) {
-    if (!plan_header_ok(plan) || !mipx::ycc_input_layout(layout)) return MIPX_EINVAL;
-    if (plan->in_bands != 3) {
-        mipx::set_error("%s: the plan takes %d bands, %s makes 3", who, plan->in_bands,
-                        op == MIPX_OP_YCC ? "planar YCbCr" : "a YCbCr JPEG");
+    if (!plan_header_ok(plan)) return MIPX_EINVAL;
+    if (!(op == MIPX_OP_YCC ? mipx::ycc_input_layout(layout) : mipx::jpeg_input_layout(layout))) return MIPX_EINVAL;
+    const int32_t bands = mipx::jpeg_layout_bands(layout);
+    if (plan->in_bands != bands) {
+        mipx::set_error("%s: the plan takes %d bands, %s makes %d", who, plan->in_bands,
+                        op == MIPX_OP_YCC ? "planar YCbCr" : bands == 1 ? "a grey JPEG" : "a YCbCr JPEG", bands);
         return MIPX_EINVAL;
     }
     if (plan->n_steps > 0 && (plan->steps[0].op == MIPX_OP_YCC || plan->steps[0].op == MIPX_OP_JPEGD ||
@@ -792,7 +802,7 @@ static int prepend_jpeg_step(mipx_plan *plan, const char *who, int32_t op, int32
     s.op = op;
     s.a[0] = layout;
     if (shrink != 1) s.a[1] = shrink, s.a[2] = file_w, s.a[3] = file_h;
-    s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = 3;
+    s.out_w = plan->in_w, s.out_h = plan->in_h, s.out_bands = bands;
     return MIPX_OK;
 }
 

@@ -11,12 +11,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._abi import (MipxCfg, MipxImg, MipxInput, MipxOpts, MipxPlan, check, lib, MipxError,
-                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, OP_JPEGH, YCC_444, YCC_420, YCC_422,
+                   EXTEND, GRAVITY, TYPES, OP_YCC, OP_JPEGC, OP_JPEGD, OP_JPEGRT, OP_JPEGE, OP_JPEGH, YCC_444, YCC_420, YCC_422, YCC_GREY,
                    JPEG_SCAN_HEADER_BYTES, JPEG_SCAN_OPT_HEADER_BYTES, JPEGH_OK, JPEGH_UNSYNCED, JPEGH_BAD, sync_tuning)
 
 __all__ = ["DeviceBuffer", "GuardedBuffer", "guard_damage", "set_guard", "guard_setting", "guarded_calls",
            "make_opts", "make_input", "plan_make", "plan_textmark_geometry", "plan_add_textmark",
-           "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420", "YCC_422",
+           "plan_set_ycc_input", "ycc_bytes", "ycc_to_rgb", "YCC_444", "YCC_420", "YCC_422", "YCC_GREY",
            "plan_set_jpegc_output", "jpegc_bytes", "jpeg_qtables", "rgb_to_jpegc",
            "plan_set_jpegd_input", "plan_set_jpegd_input_scaled", "jpegd_bytes", "jpegd_to_rgb", "jpegd_to_rgb_scaled",
            "plan_add_jpeg_roundtrip", "jpeg_roundtrip",
@@ -337,7 +337,7 @@ def jpegd_bytes(w: int, h: int, layout: int) -> int:
 def plan_set_jpegd_input(plan: MipxPlan, layout: int) -> MipxPlan:
     """mipx_plan_set_jpegd_input on `plan` (in place; returned for convenience): the plan then
     takes a JPEG's quantisation tables and quantised coefficients (codec.decode_jpeg_coefs;
-    YCC_444, YCC_420 or YCC_422) instead of RGB pixels."""
+    YCC_444, YCC_420 or YCC_422) instead of RGB pixels; a 1-band plan takes YCC_GREY."""
     check(lib.mipx_plan_set_jpegd_input(C.byref(plan), layout), "mipx_plan_set_jpegd_input")
     return plan
 
@@ -382,7 +382,7 @@ def jpeg_qtables(quality: int):
 
 def plan_set_jpegc_output(plan: MipxPlan, layout: int, quality: int) -> MipxPlan:
     """mipx_plan_set_jpegc_output on `plan` (in place; returned for convenience): the plan then
-    gives the quantised DCT coefficients of its 3-band result (YCC_444 or YCC_420, made at
+    gives the quantised DCT coefficients of its 3-band result (YCC_444 or YCC_420; YCC_GREY of a 1-band one; made at
     `quality`) instead of RGB pixels."""
     check(lib.mipx_plan_set_jpegc_output(C.byref(plan), layout, quality), "mipx_plan_set_jpegc_output")
     return plan
@@ -415,7 +415,7 @@ def jpeg_scan_opt_bytes(w: int, h: int, layout: int) -> int:
 
 def plan_set_jpeg_scan_output(plan: MipxPlan, layout: int, quality: int, optimize: bool = False) -> MipxPlan:
     """mipx_plan_set_jpeg_scan_output on `plan` (in place; returned for convenience): the plan then
-    gives the finished entropy-coded scan of its 3-band result (YCC_444 or YCC_420, made at
+    gives the finished entropy-coded scan of its 3-band result (YCC_444 or YCC_420; YCC_GREY of a 1-band one; made at
     `quality`), one slot per image (scan_slot reads it), instead of RGB pixels.  optimize: coded with
     the image's own Huffman tables, which the slot then carries (mipx_plan_set_jpeg_scan_output_optimized)."""
     if optimize:
@@ -509,7 +509,7 @@ class Engine:
         re-read in Engine(), run_op and execute, not per request: a reload
         must not race the queue workers' launches."""
         planar = _packed_input(plan)
-        if planar:  # the packed planes or the payload of one image, described as the plan's w x h x 3
+        if planar:  # the packed planes or the payload of one image, described as the plan's w x h x bands
             img = _planes(plan, img)
             if img.shape[0] != 1:
                 raise ValueError("submit takes one image's planes or payload")
@@ -518,7 +518,7 @@ class Engine:
             img = np.ascontiguousarray(img, dtype=np.uint8)  # rows may keep a wider stride
         coefs = _jpegc_layout(plan)
         scan = _jpege_layout(plan)
-        if coefs is not None:  # the coefficients of one image, described as the plan's w x h x 3
+        if coefs is not None:  # the coefficients of one image, described as the plan's w x h x bands
             shape, dtype = (jpegc_bytes(plan.out_w, plan.out_h, coefs) // 2,), np.int16
         elif scan is not None:  # ... or its slot
             shape, dtype = (_jpege_slot_bytes(plan),), np.uint8
@@ -531,9 +531,9 @@ class Engine:
         ti = C.c_uint64()
         wm = np.ascontiguousarray(wm, dtype=np.uint8) if wm is not None else None  # a copy must live until the submit
         wmi = C.byref(_img(wm)) if wm is not None else None
-        src = MipxImg(img.ctypes.data, plan.in_w, plan.in_h, 3, 0) if planar else _img(img)
+        src = MipxImg(img.ctypes.data, plan.in_w, plan.in_h, plan.in_bands, 0) if planar else _img(img)
         packed = coefs is not None or scan is not None
-        dst = MipxImg(out.ctypes.data, plan.out_w, plan.out_h, 3, 0) if packed else _img(out)
+        dst = MipxImg(out.ctypes.data, plan.out_w, plan.out_h, plan.out_bands, 0) if packed else _img(out)
         check(lib.mipx_submit(device, C.byref(plan), C.byref(src), wmi, C.byref(dst),
                               C.byref(ti)), "mipx_submit")
         return ti.value, out
@@ -702,15 +702,16 @@ def ycc_to_rgb(planes: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
 
 def rgb_to_jpegc(imgs: np.ndarray, layout: int, quality: int) -> np.ndarray:
     """mipx_op_rgb_to_jpegc on (h, w, 3) or (n, h, w, 3) uint8; returns the coefficients,
-    (n, jpegc_bytes / 2) int16."""
+    (n, jpegc_bytes / 2) int16.  With YCC_GREY the images are (n, h, w, 1)."""
     sync_tuning()
     x = _batch(imgs)
     n, h, w, b = x.shape
     need = jpegc_bytes(w, h, layout)
-    if b != 3 or need == 0:
-        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
+    if b != (1 if layout == YCC_GREY else 3) or need == 0:
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420, "
+                         "or 1 band and YCC_GREY")
     what = "mipx_op_rgb_to_jpegc"
-    din = _dev("in", what, x.nbytes, w * 3, x)
+    din = _dev("in", what, x.nbytes, w * b, x)
     dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
     check(lib.mipx_op_rgb_to_jpegc(din.ptr, dout.ptr, n, w, h, layout, quality, None), what)
     synchronize()
@@ -726,10 +727,11 @@ def rgb_to_jpeg_scan(imgs: np.ndarray, layout: int, quality: int, optimize: bool
     x = _batch(imgs)
     n, h, w, b = x.shape
     need = (jpeg_scan_opt_bytes if optimize else jpeg_scan_bytes)(w, h, layout)
-    if b != 3 or need == 0:
-        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
+    if b != (1 if layout == YCC_GREY else 3) or need == 0:
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420, "
+                         "or 1 band and YCC_GREY")
     what = "mipx_op_rgb_to_jpeg_scan_optimized" if optimize else "mipx_op_rgb_to_jpeg_scan"
-    din = _dev("in", what, x.nbytes, w * 3, x)
+    din = _dev("in", what, x.nbytes, w * b, x)
     dout = _dev("out", what, n * need, 128 * ((w + 7) // 8))
     ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 1.0 if optimize else 0.0, 0.0))
     check(getattr(lib, what)(din.ptr, dout.ptr, n, w, h, layout, quality, ws.ptr, None), what)
@@ -782,10 +784,11 @@ def rgb_to_jpeg_scan_packed(imgs: np.ndarray, layout: int, quality: int, optimiz
     x = _batch(imgs)
     n, h, w, b = x.shape
     need = (jpeg_scan_opt_bytes if optimize else jpeg_scan_bytes)(w, h, layout)
-    if b != 3 or need == 0:
-        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420")
+    if b != (1 if layout == YCC_GREY else 3) or need == 0:
+        raise ValueError(f"images of shape {np.shape(imgs)}, layout {layout}: RGB and YCC_444 / YCC_420, "
+                         "or 1 band and YCC_GREY")
     what = "mipx_op_rgb_to_jpeg_scan_packed"
-    din = _dev("in", what, x.nbytes, w * 3, x)
+    din = _dev("in", what, x.nbytes, w * b, x)
     ws = _dev("ws", what, lib.mipx_op_workspace_bytes(OP_JPEGE, n, w, h, 3, 1.0 if optimize else 0.0, 0.0))
     out = _packed_result(what, n, need, lambda dout, ddir: lib.mipx_op_rgb_to_jpeg_scan_packed(
         din.ptr, dout.ptr, n, w, h, layout, quality, ws.ptr, None, int(bool(optimize)), ddir), w, din, ws)
@@ -824,7 +827,8 @@ def scan_unpack(dir, packed, i: int, head: int, slot_bytes: int) -> np.ndarray:
 
 
 def jpegd_to_rgb(payload: np.ndarray, w: int, h: int, layout: int) -> np.ndarray:
-    """mipx_op_jpegd_to_rgb on coefficient payloads, (bytes,) or (n, bytes) uint8; returns (n, h, w, 3)."""
+    """mipx_op_jpegd_to_rgb on coefficient payloads, (bytes,) or (n, bytes) uint8; returns (n, h, w, 3),
+    with YCC_GREY (n, h, w, 1)."""
     sync_tuning()
     x = np.ascontiguousarray(payload, dtype=np.uint8)
     if x.ndim == 1:
@@ -835,18 +839,19 @@ def jpegd_to_rgb(payload: np.ndarray, w: int, h: int, layout: int) -> np.ndarray
     n = x.shape[0]
     what = "mipx_op_jpegd_to_rgb"
     din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
-    dout = _dev("out", what, n * h * w * 3, w * 3)
+    b = 1 if layout == YCC_GREY else 3
+    dout = _dev("out", what, n * h * w * b, w * b)
     wsb = lib.mipx_op_workspace_bytes(OP_JPEGD, n, w, h, 3, 0.0, 0.0)
     ws = _dev("ws", what, wsb)
     check(lib.mipx_op_jpegd_to_rgb(din.ptr, dout.ptr, n, w, h, layout, ws.ptr, wsb, None), what)
     synchronize()
     _check_guards(what, din, dout, ws)
-    return dout.download((n, h, w, 3))
+    return dout.download((n, h, w, b))
 
 
 def jpegd_to_rgb_scaled(payload: np.ndarray, w: int, h: int, layout: int, shrink: int) -> np.ndarray:
     """mipx_op_jpegd_to_rgb_scaled on the coefficient payloads of w x h files, (bytes,) or
-    (n, bytes) uint8; returns (n, ceil(h / shrink), ceil(w / shrink), 3)."""
+    (n, bytes) uint8; returns (n, ceil(h / shrink), ceil(w / shrink), 3), with YCC_GREY 1 band."""
     sync_tuning()
     x = np.ascontiguousarray(payload, dtype=np.uint8)
     if x.ndim == 1:
@@ -858,13 +863,14 @@ def jpegd_to_rgb_scaled(payload: np.ndarray, w: int, h: int, layout: int, shrink
     n, ow, oh = x.shape[0], -(-w // shrink), -(-h // shrink)
     what = "mipx_op_jpegd_to_rgb_scaled"
     din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
-    dout = _dev("out", what, n * oh * ow * 3, ow * 3)
+    b = 1 if layout == YCC_GREY else 3
+    dout = _dev("out", what, n * oh * ow * b, ow * b)
     wsb = lib.mipx_op_workspace_bytes(OP_JPEGD, n, ow, oh, 3, 0.0, 0.0)
     ws = _dev("ws", what, wsb)
     check(lib.mipx_op_jpegd_to_rgb_scaled(din.ptr, dout.ptr, n, w, h, layout, shrink, ws.ptr, wsb, None), what)
     synchronize()
     _check_guards(what, din, dout, ws)
-    return dout.download((n, oh, ow, 3))
+    return dout.download((n, oh, ow, b))
 
 
 def jpegh_bytes(w: int, h: int, layout: int) -> int:
@@ -913,7 +919,8 @@ def jpegh_to_rgb_scaled(slots: np.ndarray, w: int, h: int, layout: int, shrink: 
     n, ow, oh = x.shape[0], -(-w // shrink), -(-h // shrink)
     what = "mipx_op_jpegh_to_rgb" if _full else "mipx_op_jpegh_to_rgb_scaled"
     din = _dev("in", what, x.nbytes, 128 * ((w + 7) // 8), x)
-    dout = _dev("out", what, n * oh * ow * 3, ow * 3)
+    b = 1 if layout == YCC_GREY else 3   # a grey file decodes to its one plane
+    dout = _dev("out", what, n * oh * ow * b, ow * b)
     dst = _dev("status", what, 4 * n)
     wsb = lib.mipx_op_workspace_bytes(OP_JPEGH, n, w, h, 3, 0.0, 0.0)
     ws = _dev("ws", what, wsb)
@@ -923,7 +930,7 @@ def jpegh_to_rgb_scaled(slots: np.ndarray, w: int, h: int, layout: int, shrink: 
         check(lib.mipx_op_jpegh_to_rgb_scaled(din.ptr, dout.ptr, dst.ptr, n, w, h, layout, shrink, ws.ptr, wsb, None), what)
     synchronize()
     _check_guards(what, din, dout, dst, ws)
-    return dout.download((n, oh, ow, 3)), dst.download((n,), np.uint32)
+    return dout.download((n, oh, ow, b)), dst.download((n,), np.uint32)
 
 
 def jpegh_to_rgb(slots: np.ndarray, w: int, h: int, layout: int):

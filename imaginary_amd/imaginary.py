@@ -516,7 +516,7 @@ class JpegScan:
 def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = None, chain: Optional[list] = None,
             text: Optional[TextMark] = None, ycc: Optional[tuple] = None, jpeg_quality: Optional[int] = None,
             jpeg_dct: Optional[tuple] = None, jpeg_dct_shrink: bool = False, jpeg_scan: bool = False,
-            jpeg_huff: Optional[tuple] = None, jpeg_optimize: bool = False):
+            jpeg_huff: Optional[tuple] = None, jpeg_optimize: bool = False, jpeg_grey: bool = False):
     """image.go:81-113 Process with bimg.Resize's pixel work on the GPU.
 
     Encoded bytes in -> Image out (the drop-in: host codec, engine, host codec);
@@ -548,7 +548,9 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
     uncodable coefficient makes the request run again with the coefficient step.  With
     `jpeg_optimize` besides `jpeg_scan`, the scan is coded with the image's own optimised Huffman
     tables (libjpeg's optimize_coding) and the JpegScan carries them; a result too large for that
-    step (10^9 / 64 scan blocks or more) goes to the coefficient step like a slot that is not OK."""
+    step (10^9 / 64 scan blocks or more) goes to the coefficient step like a slot that is not OK.
+    With `jpeg_grey` besides `jpeg_quality`, a 1-band result ends the plan with the grey coefficient
+    step or scan step (codec.YCC_GREY) and comes back as a JpegCoefs or JpegScan as well."""
     if isinstance(img, (bytes, bytearray, memoryview)):
         return process_bytes(bytes(img), opts, wm, text)
     if isinstance(img, _Staged):
@@ -596,8 +598,10 @@ def process(img, opts: Dict[str, Any], wm=None, redecode: Optional[Decoder] = No
         if chain is not None:
             chain.append((plan, px, wm))
             return _placeholder(plan.out_h, plan.out_w, plan.out_bands)
-        if jpeg_quality is not None and plan.out_bands == 3:
+        if jpeg_quality is not None and (plan.out_bands == 3 or (jpeg_grey and plan.out_bands == 1)):
             layout = codec.YCC_444 if jpeg_quality >= 90 else codec.YCC_420
+            if plan.out_bands == 1:
+                layout = codec.YCC_GREY
             if jpeg_scan:
                 coded = _abi.MipxPlan()
                 C.memmove(C.byref(coded), C.byref(plan), C.sizeof(plan))
@@ -628,7 +632,7 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
                   ycc: bool = False, jpeg_coefs: bool = False, jpeg_dct: bool = False,
                   jpeg_dct_shrink: bool = False, device_reencode: bool = False, jpeg_scan: bool = False,
                   jpeg_huff: bool = False, jpeg_huff_restart: bool = False, jpeg_optimize: bool = False,
-                  jpeg_422: bool = False) -> Image:
+                  jpeg_422: bool = False, jpeg_grey: bool = False) -> Image:
     """Process(buf, opts) over encoded bytes: header -> plan -> decode (with the
     plan's shrink-on-load) -> engine -> encode; WEBP/HEIF/AVIF encode failures
     retry as JPEG (image.go:97-107); MIME from the output bytes (image.go:109-112).
@@ -667,6 +671,12 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
     the engine's MIPX_YCC_422 input layout); everything those flags do is done for such a file as well,
     and the bytes are the same either way.  `ycc` does not take 4:2:2: the stand-in decoder cannot hand
     out its raw chroma planes.
+    jpeg_grey: jpeg_dct and jpeg_huff (with jpeg_dct_shrink and jpeg_huff_restart as they are set)
+    take one-component JPEGs too (codec.decode_jpeg_coefs / jpeg_huff_slot with grey=True; the
+    engine's MIPX_YCC_GREY layout, a 1-band plan), and jpeg_coefs, jpeg_scan and jpeg_optimize take
+    1-band answers, the answer of a colorspace=bw request on a colour input among them: the
+    one-component file codec.encode writes; the bytes are the same either way.  `ycc` and
+    `device_reencode` do not take grey.
     device_reencode: a 3-band JPEG that rotates and shrinks on load (_rotate_reencode_shrink_on_load)
     runs as one plan, the re-encode and the scaled decode as a MIPX_OP_JPEGRT step between the
     rotation and the rest: one upload, no host codec in between; the bytes are the same either way."""
@@ -700,59 +710,74 @@ def process_bytes(buf: bytes, opts: Dict[str, Any], wm=None, text: Optional[Text
             raise EngineUnsupported(str(e)) from e
         raise ImaginaryError(f"image processing error: {e}", 500) from e
     rotates = any(step[0] in ("rot", "flip") for step in plan.describe())
+    takes_bands = hdr.bands == 3 or (jpeg_grey and hdr.bands == 1)   # what the engine's JPEG input steps take
+    grey = {"jpeg_grey": True} if jpeg_grey else {}   # a request without the option makes the calls it always made
     if plan.load_shrink > 1 and itype == "jpeg" and rotates and not opts.get("no_auto_rotate"):
         px = _rotate_reencode_shrink_on_load(buf, hdr, itype, opts, wm_px, text, device=device_reencode)
     elif plan.load_shrink > 1:  # process() re-plans on the codec-shrunk size
-        take = (jpeg_dct or jpeg_huff) and jpeg_dct_shrink and hdr.bands == 3 and itype == "jpeg" and not rotates
+        take = (jpeg_dct or jpeg_huff) and jpeg_dct_shrink and takes_bands and itype == "jpeg" and not rotates
         src = Decoded(np.zeros((1, 1, hdr.bands), np.uint8), itype, hdr.orientation, hdr.w, hdr.h)
         px = None
         if take and jpeg_huff:
-            px = _with_scan(buf, jpeg_huff_restart, jpeg_422,
+            px = _with_scan(buf, jpeg_huff_restart, jpeg_422, jpeg_grey,
                             lambda slot: process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq,
-                                                 jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize))
+                                                 jpeg_huff=slot, jpeg_dct_shrink=True, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize, **grey))
         if px is None:
-            dct = _coefs(buf, jpeg_422) if take else None
+            dct = _coefs(buf, jpeg_422, jpeg_grey) if take else None
             px = process(src, opts, wm=wm_px, redecode=redecode, text=text, jpeg_quality=jq, jpeg_dct=dct,
-                         jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
+                         jpeg_dct_shrink=dct is not None, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize, **grey)
     else:
-        take = (jpeg_dct or jpeg_huff) and hdr.bands == 3 and itype == "jpeg"
+        take = (jpeg_dct or jpeg_huff) and takes_bands and itype == "jpeg"
         px = None
         if take and jpeg_huff:
-            px = _with_scan(buf, jpeg_huff_restart, jpeg_422,
-                            lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts,
-                                                 wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize))
-        dct = _coefs(buf, jpeg_422) if take and px is None else None
+            px = _with_scan(buf, jpeg_huff_restart, jpeg_422, jpeg_grey,
+                            lambda slot: process(Decoded(_placeholder(hdr.h, hdr.w, hdr.bands), itype, hdr.orientation), opts,
+                                                 wm=wm_px, text=text, jpeg_huff=slot, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize, **grey))
+        dct = _coefs(buf, jpeg_422, jpeg_grey) if take and px is None else None
         planes = codec.decode_ycc(buf) if px is None and dct is None and ycc and hdr.bands == 3 else None
         if px is not None:
             pass
         elif dct is not None:
-            px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         jpeg_dct=dct, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
+            px = process(Decoded(_placeholder(hdr.h, hdr.w, hdr.bands), itype, hdr.orientation), opts, wm=wm_px, text=text,
+                         jpeg_dct=dct, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize, **grey)
         elif planes is not None:
             px = process(Decoded(_placeholder(hdr.h, hdr.w, 3), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         ycc=planes, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
+                         ycc=planes, jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize, **grey)
         else:
             px = process(Decoded(codec.decode(buf), itype, hdr.orientation), opts, wm=wm_px, text=text,
-                         jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize)
+                         jpeg_quality=jq, jpeg_scan=jpeg_scan, jpeg_optimize=jpeg_optimize, **grey)
+    if isinstance(px, JpegScan) and px.layout == codec.YCC_GREY:   # the factors codec.encode's file declares, as below
+        body = codec.jpeg_from_scan(px.scan, px.w, px.h, px.layout, px.quality, px.tables,
+                                    grey_sampling=1 if px.quality >= 90 else 2)
+        return Image(body, codec.mime_type(codec.sniff_type(body)))
     if isinstance(px, JpegScan):
         body = codec.jpeg_from_scan(px.scan, px.w, px.h, px.layout, px.quality, px.tables)
         return Image(body, codec.mime_type(codec.sniff_type(body)))
     if isinstance(px, JpegCoefs):
-        body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)
+        if px.layout == codec.YCC_GREY:   # the factors codec.encode's file declares: it asks for 4:2:0 below Q 90
+            body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality,
+                                           grey_sampling=1 if px.quality >= 90 else 2)
+        else:
+            body = codec.encode_jpeg_coefs(px.coefs, px.w, px.h, px.layout, px.quality)
         return Image(body, codec.mime_type(codec.sniff_type(body)))
     return _encode(px, t, quality, compression)
 
 
-def _coefs(buf: bytes, h2v1: bool):
-    """codec.decode_jpeg_coefs, of 4:2:2 files too when the request opted in; the call without the
-    option stays the call it always was."""
+def _coefs(buf: bytes, h2v1: bool, grey: bool = False):
+    """codec.decode_jpeg_coefs, of 4:2:2 and of grey files too when the request opted in; the call
+    without the options stays the call it always was."""
+    if grey:
+        return codec.decode_jpeg_coefs(buf, h2v1=h2v1, grey=True)
     return codec.decode_jpeg_coefs(buf, h2v1=True) if h2v1 else codec.decode_jpeg_coefs(buf)
 
 
-def _with_scan(buf: bytes, restart: bool, h2v1: bool, run):
+def _with_scan(buf: bytes, restart: bool, h2v1: bool, grey: bool, run):
     """run((slot, layout)) of the file's entropy-coded scan; None where the file has no slot
     (codec.jpeg_huff_slot) or the engine could not decode it, and the caller goes on without."""
-    slot = codec.jpeg_huff_slot(buf, restart=restart, h2v1=True) if h2v1 else codec.jpeg_huff_slot(buf, restart=restart)
+    if grey:
+        slot = codec.jpeg_huff_slot(buf, restart=restart, h2v1=h2v1, grey=True)
+    else:
+        slot = codec.jpeg_huff_slot(buf, restart=restart, h2v1=True) if h2v1 else codec.jpeg_huff_slot(buf, restart=restart)
     if slot is None:
         return None
     try:

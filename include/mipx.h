@@ -145,11 +145,12 @@ enum {
                                                      (libjpeg upsample + colour conversion) */
     MIPX_OP_JPEGC,       /* a[0] = MIPX_YCC_*, a[1] = quality 1..100; out_w/out_h/out_bands = the image it
                             consumes (w, h, 3); only as the LAST step of a plan whose image there has 3
-                            bands; the output buffer is then the quantised coefficients
+                            bands (MIPX_YCC_GREY: 1 band, and out_bands = 1); the output buffer is then
+                            the quantised coefficients
                             (mipx_plan_set_jpegc_output)
                                   (libjpeg colour conversion, downsample, forward DCT, quantisation) */
-    MIPX_OP_JPEGD,       /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan, never together
-                            with MIPX_OP_YCC; the input buffer is then the file's quantisation tables and
+    MIPX_OP_JPEGD,       /* a[0] = MIPX_YCC_*; out_bands = 3; only as step 0 of a 3-band plan (MIPX_YCC_GREY:
+                            out_bands = 1, of a 1-band plan), never together with MIPX_OP_YCC; the input buffer is then the file's quantisation tables and
                             quantised coefficients (mipx_plan_set_jpegd_input)
                                   (libjpeg dequantisation, inverse DCT, upsample, colour conversion)
                             a[1] = shrink: 0 or 1 decode at full size; 2, 4, 8 decode at that fraction
@@ -166,7 +167,8 @@ enum {
                             the Annex K Huffman tables or 1 for the image's own optimised ones (any other value
                             is MIPX_EINVAL: this tightens a word that was ignored); out_w/out_h/
                             out_bands = the image it consumes (w, h, 3); only as the LAST step of a plan whose
-                            image there has 3 bands, never together with MIPX_OP_JPEGC; the output buffer is
+                            image there has 3 bands (MIPX_YCC_GREY: 1 band, and out_bands = 1), never
+                            together with MIPX_OP_JPEGC; the output buffer is
                             then one slot per image (mipx_plan_set_jpeg_scan_output)
                                   (MIPX_OP_JPEGC's rule, then libjpeg's baseline Huffman coder) */
     MIPX_OP_JPEGH        /* = 20, entropy-coded JPEG input (see MIPX_JPEGH_HEADER_BYTES): a[] exactly as
@@ -186,8 +188,14 @@ enum {
  * cw <= 2) and converts with libjpeg's integer YCbCr -> RGB, bit for bit
  * (PARITY_ASSUMPTIONS.md rows 16 and 25).  MIPX_YCC_422 is an input layout only: every call
  * and plan step that writes a JPEG (MIPX_OP_JPEGC, MIPX_OP_JPEGE, MIPX_OP_JPEGRT) rejects it.
- * The value 2 is deliberately unused: it has always been an unknown layout and stays one. */
-enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1, MIPX_YCC_422 = 3 };
+ * The value 2 is deliberately unused: it has always been an unknown layout and stays one.
+ *    MIPX_YCC_GREY is a one-component (greyscale) JPEG: its single plane is the 1-band image, so
+ * there is nothing to upsample or convert, and MIPX_OP_YCC and MIPX_OP_JPEGRT reject it.  The steps
+ * that read or write a file take it (MIPX_OP_JPEGD, MIPX_OP_JPEGH, MIPX_OP_JPEGC, MIPX_OP_JPEGE),
+ * on 1 band only, and their out_bands is then 1: grey goes with 1 band and the other layouts with
+ * 3, every other pairing is MIPX_EINVAL (PARITY_ASSUMPTIONS.md row 26).  Its value is 6 because
+ * -1, 2, 4, 5, 7 and 1 << 20 have always been unknown layouts and stay so. */
+enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1, MIPX_YCC_422 = 3, MIPX_YCC_GREY = 6 };
 
 /* JPEG coefficient output (MIPX_OP_JPEGC): what a JPEG encoder has in front of its entropy
  * coder, so the host only Huffman-codes (libjpeg jpeg_write_coefficients).  The same two
@@ -201,7 +209,11 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1, MIPX_YCC_422 = 3 };
  * and 4:2:2 (zero AC, DC copied) are the entropy coder's and are not emitted.  The
  * engine computes libjpeg's integer RGB -> YCbCr, its h2v2 downsample, the "islow" forward DCT
  * and the quantisation with the tables of jpeg_set_quality(quality, TRUE), bit for bit
- * (PARITY_ASSUMPTIONS.md row 17); images and both pointers start on any byte. */
+ * (PARITY_ASSUMPTIONS.md row 17); images and both pointers start on any byte.
+ *    MIPX_YCC_GREY (libjpeg's JCS_GRAYSCALE): the input is 1-band pixels, w * h bytes per image, and
+ * the output is Y's blocks alone, 128 * ceil(w / 8) * ceil(h / 8) bytes: sample - 128 with the last
+ * column and row repeated, the same forward DCT, the luminance table (PARITY_ASSUMPTIONS.md row 26).
+ * Grey goes with 1 band and the other layouts with 3: every other pairing is MIPX_EINVAL. */
 /* JPEG coefficient input (MIPX_OP_JPEGD): what a JPEG decoder has behind its entropy decoder
  * (libjpeg jpeg_read_coefficients), so the host only Huffman-decodes.  One image is a 384-byte
  * header followed by the coefficients.  The header is the file's quantisation tables of Y, Cb and
@@ -227,7 +239,13 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1, MIPX_YCC_422 = 3 };
  * wide, the MIPX_YCC_422 planes of the decoded size, and is upsampled as MIPX_OP_YCC does at
  * that size; at 1 / 8 by plain replication at every width, as libjpeg switches the fancy
  * upsampler off there.  Bit for bit libjpeg-turbo's on files an encoder writes,
- * tests/jpegds_ref.py's rule elsewhere (PARITY_ASSUMPTIONS.md rows 19 and 25). */
+ * tests/jpegds_ref.py's rule elsewhere (PARITY_ASSUMPTIONS.md rows 19 and 25).
+ *    MIPX_YCC_GREY: the 384-byte header stays; only its first 128 bytes (Y's table) are read and the
+ * host writes zeros behind them.  Then Y's coefficients: hb x wb blocks in raster order, natural order
+ * inside a block.  The step is step 0 of a 1-band plan and its out_bands is 1: the decoded plane,
+ * ceil(w / s) x ceil(h / s) from the 8 / s point inverse DCT, is the image, written straight to the
+ * step's output (at 1 / 8 it is the block grid's DC terms).  The op calls write n * ow * oh bytes.
+ * The workspace a 3-band call needs stays sufficient and is still asked for (row 26). */
 /* JPEG round trip (MIPX_OP_JPEGRT): what re-encoding an image as a JPEG and decoding that file
  * does to its pixels, as imaginary's /pipeline does between stages and bimg does before a rotated
  * JPEG shrinks on load, without the file: exactly MIPX_OP_JPEGC's rule at (layout, quality), then
@@ -266,6 +284,12 @@ enum { MIPX_YCC_444 = 0, MIPX_YCC_420 = 1, MIPX_YCC_422 = 3 };
  * other; the scan starts at byte 1104.  The statuses mean what they mean above (a value without an
  * Annex K code has no code here either); when the status is not OK the tables are unspecified.
  * A scan of 64 x blocks >= 10^9 (libjpeg's search starts there) is MIPX_EINVAL for this variant.
+ *    MIPX_YCC_GREY: the input is 1-band pixels (n * w * h bytes) or Y's coefficients alone, and the scan
+ * is the one libjpeg writes for JCS_GRAYSCALE: not interleaved, ceil(w / 8) x ceil(h / 8) MCUs of one
+ * block each in raster order, no dummy blocks, tables 0/0.  The 16- and 1104-byte headers stay; with
+ * optimised tables DC 0 and AC 0 stand at their places and the places of DC 1 and AC 1 are all zero,
+ * which is "a table the file does not define" in a MIPX_OP_JPEGH slot, so one still copies into the
+ * other.  The host writes one DQT, an SOF0 and an SOS of one component, and DHT DC 0 and AC 0 only.
  *    Packed slots (mipx_op_rgb_to_jpeg_scan_packed, mipx_op_jpegc_to_scan_packed; what the request path
  * downloads): the same slots back to back in the same output buffer, each rounded up to 16 bytes, behind a
  * directory of n + 1 uint64 byte offsets; a slot is then its header (and tables) and its `length` bytes, a
@@ -311,7 +335,14 @@ enum { MIPX_JPEG_SCAN_OK = 0, MIPX_JPEG_SCAN_OVERFLOW = 1, MIPX_JPEG_SCAN_UNCODA
  * DC symbol above 15; a scan that ends before its last block; a DC outside int16.  (A run of 16
  * zeros that passes coefficient 63 ends the block, as in libjpeg.)  Bits behind the last block are
  * ignored.  The payload of an image whose status is not OK is unspecified, but every write stays
- * inside it. */
+ * inside it.
+ *    MIPX_YCC_GREY: a scan of one component, which is not interleaved.  The 1504-byte header stays:
+ * Y's quantisation table at byte 16 with zeros behind it; byte 400 is Y's DC table index and byte
+ * 403 its AC index, and the other four bytes are ignored; all four table places may be filled,
+ * because a file may define table 1 and use it.  M = ceil(w / 8) ceil(h / 8) MCUs of one block each
+ * in raster order, no dummy blocks; a restart interval counts blocks; the DC predictor is the one
+ * component's.  Every status and every BAD condition keeps its meaning.  The payload is
+ * MIPX_OP_JPEGD's for the layout, and the op calls that go on to pixels write n * ow * oh bytes. */
 #define MIPX_JPEGH_HEADER_BYTES 1504
 enum { MIPX_JPEGH_OK = 0, MIPX_JPEGH_UNSYNCED = 1, MIPX_JPEGH_BAD = 2 };
 

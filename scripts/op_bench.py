@@ -25,6 +25,7 @@ rocprofv3 passes see that kernel alone.
          jpegc420 jpegc444 jpegd420 jpegd444 jpegds420 jpegds444 jpegrt420 jpegrt444
          jpege420 jpege444 jpegcs420 jpegcs444 jpegh420 jpegh444 jpeghd420 jpeghd444
          ycc422 jpegd422 jpegds422 jpegh422 jpeghd422 (input only; jpegh422 / jpeghd422 need --restart)
+         jpegcgrey jpegdgrey jpegdsgrey jpegegrey jpegcsgrey jpeghgrey jpeghdgrey (MIPX_YCC_GREY: 1-band pixels)
 """
 import argparse
 import ctypes as C
@@ -116,39 +117,43 @@ def main():
         ob = b if b in (2, 4) else b + 1
         mask = torch.randint(0, 256, (mh * mw * 4,), dtype=torch.uint8, device=dev)
     in_img = w * h * b          # input bytes of one image
-    LAYOUT = {"420": 1, "444": 0, "422": 3}   # MIPX_YCC_*, by the op's last three characters
+    LAYOUT = {"420": 1, "444": 0, "422": 3, "rey": 6}   # MIPX_YCC_*, by the op's last three characters (grey)
+    grey = a.op.endswith("grey")
+    pb = 1 if grey else 3       # bands of the pixels beside a JPEG of the op's layout
     if a.op in ("ycc420", "ycc444", "ycc422"):   # packed JPEG planes in, RGB out
         b = ob = 3
         layout = LAYOUT[a.op[-3:]]
         in_img = lib.mipx_ycc_bytes(w, h, layout)
     out_img = ow * oh * ob      # output bytes of one image
-    if a.op in ("jpegc420", "jpegc444"):   # RGB in, quantised DCT coefficients out
-        b = ob = 3              # "out" names the image the step consumes; its bytes are out_img
-        layout = 1 if a.op == "jpegc420" else 0
-        in_img, out_img = w * h * 3, lib.mipx_jpegc_bytes(w, h, layout)
-    JPEGD = ("jpegd420", "jpegd444", "jpegd422", "jpegds420", "jpegds444", "jpegds422")
+    if a.op in ("jpegc420", "jpegc444", "jpegcgrey"):   # RGB in, quantised DCT coefficients out
+        b = ob = pb             # "out" names the image the step consumes; its bytes are out_img
+        layout = LAYOUT[a.op[-3:]]
+        in_img, out_img = w * h * pb, lib.mipx_jpegc_bytes(w, h, layout)
+    JPEGD = ("jpegd420", "jpegd444", "jpegd422", "jpegdgrey", "jpegds420", "jpegds444", "jpegds422", "jpegdsgrey")
     if a.op in JPEGD:   # quantisation tables + quantised DCT coefficients in, RGB out
-        b = ob = 3
+        b = ob = pb
         layout = LAYOUT[a.op[-3:]]
         in_img = lib.mipx_jpegd_bytes(w, h, layout)
+        if grey:
+            out_img = ow * oh
         if a.op.startswith("jpegds"):   # ... at 1/shrink: the same payload, RGB at the decoded size
             ow, oh = -(-w // a.shrink), -(-h // a.shrink)
-            out_img = ow * oh * 3
+            out_img = ow * oh * pb
     if a.op in ("jpegrt420", "jpegrt444"):   # RGB in, RGB out at 1/shrink; the planes in between are not credited
         b = ob = 3
         layout = 1 if a.op == "jpegrt420" else 0
         ow, oh = -(-w // a.shrink), -(-h // a.shrink)
         in_img, out_img = w * h * 3, ow * oh * 3
-    JPEGE = ("jpege420", "jpege444", "jpegcs420", "jpegcs444")
+    JPEGE = ("jpege420", "jpege444", "jpegegrey", "jpegcs420", "jpegcs444", "jpegcsgrey")
     if a.op in JPEGE:   # RGB (jpege*) or the encoder's coefficients (jpegcs*) in, one slot per image out
-        b = ob = 3
-        layout = 1 if a.op.endswith("420") else 0
-        in_img = w * h * 3 if a.op.startswith("jpege") else lib.mipx_jpegc_bytes(w, h, layout)
+        b = ob = pb
+        layout = LAYOUT[a.op[-3:]]
+        in_img = w * h * pb if a.op.startswith("jpege") else lib.mipx_jpegc_bytes(w, h, layout)
         out_img = (lib.mipx_jpeg_scan_opt_bytes if a.optimize else lib.mipx_jpeg_scan_bytes)(w, h, layout)
-    JPEGH = ("jpegh420", "jpegh444", "jpegh422", "jpeghd420", "jpeghd444", "jpeghd422")
+    JPEGH = ("jpegh420", "jpegh444", "jpegh422", "jpeghgrey", "jpeghd420", "jpeghd444", "jpeghd422", "jpeghdgrey")
     file_slot = None
     if a.op in JPEGH:   # one input slot per image in; RGB (jpegh*) or MIPX_OP_JPEGD's payload (jpeghd*) out
-        b = ob = 3
+        b = ob = pb
         layout = LAYOUT[a.op[-3:]]
         if layout == 3 and a.restart is None:
             raise SystemExit("4:2:2 scans are Pillow's: give --restart (0 for a file without markers)")
@@ -161,6 +166,8 @@ def main():
                 px = codec.decode(open(a.file, "rb").read())[:, :, :3]
             else:
                 px = np.random.default_rng(1).integers(0, 256, (h, w, 3), dtype=np.uint8)
+            if grey:
+                px = px[:, :, 1]
             kw = {}
             if a.restart.startswith("r"):
                 kw = dict(restart_marker_rows=int(a.restart[1:]))
@@ -168,23 +175,26 @@ def main():
                 kw = dict(restart_marker_blocks=int(a.restart))
             ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 1 << 26)   # noise at a high quality is a long scan
             out = io.BytesIO()
-            Image.fromarray(np.ascontiguousarray(px)).save(out, "JPEG", quality=a.q, subsampling={0: 0, 1: 2, 3: 1}[layout], **kw)
-            file_slot, layout = codec.jpeg_huff_slot(out.getvalue(), restart=True, h2v1=layout == 3)
+            if grey:
+                Image.fromarray(np.ascontiguousarray(px), "L").save(out, "JPEG", quality=a.q, **kw)
+            else:
+                Image.fromarray(np.ascontiguousarray(px)).save(out, "JPEG", quality=a.q, subsampling={0: 0, 1: 2, 3: 1}[layout], **kw)
+            file_slot, layout = codec.jpeg_huff_slot(out.getvalue(), restart=True, h2v1=layout == 3, grey=grey)
             w, h = px.shape[1], px.shape[0]
             ow, oh = w, h
         elif a.file:
             from imaginary_amd import codec
             buf = open(a.file, "rb").read()
             hd = codec.header(buf)
-            file_slot, layout = codec.jpeg_huff_slot(buf)
+            file_slot, layout = codec.jpeg_huff_slot(buf, grey=grey)
             w, h, ow, oh = hd.w, hd.h, hd.w, hd.h
         in_img = lib.mipx_jpegh_bytes(w, h, layout)
-        out_img = w * h * 3 if a.op.startswith("jpegh4") else lib.mipx_jpegd_bytes(w, h, layout)
+        out_img = lib.mipx_jpegd_bytes(w, h, layout) if a.op.startswith("jpeghd") else w * h * pb
     margin = mw if a.margin < 0 else a.margin
     colour = (C.c_int32 * 3)(255, 128, 0)
     x = torch.randint(0, 256, (n * in_img,), dtype=torch.uint8, device=dev)
     y = torch.empty((n * out_img,), dtype=torch.uint8, device=dev)
-    ws = torch.empty((n * max(w * h, ow * oh) * b + 4096,), dtype=torch.uint8, device=dev)
+    ws = torch.empty((n * max(w * h, ow * oh) * (3 if grey else b) + 4096,), dtype=torch.uint8, device=dev)   # grey: what a 3-band call brings
     if a.op in JPEGE:
         ws = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 1.0 if a.optimize else 0.0, 0.0),), dtype=torch.uint8,
                          device=dev)
@@ -202,13 +212,16 @@ def main():
             from imaginary_amd import codec
             lum, chrom = codec.jpeg_qtables(a.q)
             head = np.zeros(1504, np.uint8)
-            head[16:400] = np.array([lum, chrom, chrom], "<u2").ravel().view(np.uint8)
-            head[400:406] = [0, 1, 1, 0, 1, 1]
+            if grey:   # Y's table and zeros behind it; bytes 400 and 403 name tables 0
+                head[16:144] = np.array(lum, "<u2").view(np.uint8)
+            else:
+                head[16:400] = np.array([lum, chrom, chrom], "<u2").ravel().view(np.uint8)
+                head[400:406] = [0, 1, 1, 0, 1, 1]
             for i, key in enumerate((0x00, 0x01, 0x10, 0x11)):
                 counts, symbols = codec.HUFFMAN_TABLES[key]
                 head[416 + 272 * i:432 + 272 * i] = list(counts)
                 head[432 + 272 * i:432 + 272 * i + len(symbols)] = list(symbols)
-            px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
+            px = torch.randint(0, 256, (n * w * h * pb,), dtype=torch.uint8, device=dev)
             scans = torch.empty((n, in_img - 1504 + 16), dtype=torch.uint8, device=dev)
             ews = torch.empty((lib.mipx_op_workspace_bytes(19, n, w, h, 3, 0.0, 0.0),), dtype=torch.uint8, device=dev)
             torch.cuda.synchronize(dev)
@@ -220,9 +233,9 @@ def main():
             xv[:, 1504:] = scans[:, 16:]
             del px, scans, ews
         torch.cuda.synchronize(dev)
-    if a.op in ("jpegcs420", "jpegcs444"):
+    if a.op in ("jpegcs420", "jpegcs444", "jpegcsgrey"):
         # the coefficients the engine's own encoder makes of random pixels at --q, as for jpegd*
-        px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
+        px = torch.randint(0, 256, (n * w * h * pb,), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         assert lib.mipx_op_rgb_to_jpegc(px.data_ptr(), x.data_ptr(), n, w, h, layout, a.q, None) == 0
         check(lib.mipx_device_sync())
@@ -234,7 +247,9 @@ def main():
         lum, chrom = (C.c_uint8 * 64)(), (C.c_uint8 * 64)()
         assert lib.mipx_jpeg_qtables(a.q, lum, chrom) == 0
         head = np.concatenate([np.array(t, dtype="<u2") for t in (lum, chrom, chrom)]).view(np.uint8)
-        px = torch.randint(0, 256, (n * w * h * 3,), dtype=torch.uint8, device=dev)
+        if grey:
+            head[128:] = 0      # Y's table alone
+        px = torch.randint(0, 256, (n * w * h * pb,), dtype=torch.uint8, device=dev)
         coefs = torch.empty((n * (in_img - 384),), dtype=torch.uint8, device=dev)
         assert coefs.numel() == n * lib.mipx_jpegc_bytes(w, h, layout)
         torch.cuda.synchronize(dev)
@@ -291,29 +306,29 @@ def main():
             return lib.mipx_op_watermark(X, mask.data_ptr(), Y, n, w, h, b, mw, mh, 4, 100, 100, a.opacity, sp)
         if a.op in ("ycc420", "ycc444", "ycc422"):
             return lib.mipx_op_ycc_to_rgb(X, Y, n, w, h, layout, sp)
-        if a.op in ("jpegc420", "jpegc444"):
+        if a.op in ("jpegc420", "jpegc444", "jpegcgrey"):
             return lib.mipx_op_rgb_to_jpegc(X, Y, n, w, h, layout, a.q, sp)
-        if a.op in ("jpegd420", "jpegd444", "jpegd422"):
+        if a.op in ("jpegd420", "jpegd444", "jpegd422", "jpegdgrey"):
             return lib.mipx_op_jpegd_to_rgb(X, Y, n, w, h, layout, WS, WSB, sp)
-        if a.op in ("jpegds420", "jpegds444", "jpegds422"):
+        if a.op in ("jpegds420", "jpegds444", "jpegds422", "jpegdsgrey"):
             return lib.mipx_op_jpegd_to_rgb_scaled(X, Y, n, w, h, layout, a.shrink, WS, WSB, sp)
         if a.op in ("jpegrt420", "jpegrt444"):
             return lib.mipx_op_jpeg_roundtrip(X, Y, n, w, h, layout, a.q, a.shrink, WS, WSB, sp)
-        if a.op in ("jpege420", "jpege444") and a.packed:
+        if a.op in ("jpege420", "jpege444", "jpegegrey") and a.packed:
             return lib.mipx_op_rgb_to_jpeg_scan_packed(X, Y, n, w, h, layout, a.q, WS, sp, int(a.optimize), directory.data_ptr())
-        if a.op in ("jpegcs420", "jpegcs444") and a.packed:
+        if a.op in ("jpegcs420", "jpegcs444", "jpegcsgrey") and a.packed:
             return lib.mipx_op_jpegc_to_scan_packed(X, Y, n, w, h, layout, WS, sp, int(a.optimize), directory.data_ptr())
-        if a.op in ("jpege420", "jpege444"):
+        if a.op in ("jpege420", "jpege444", "jpegegrey"):
             if a.optimize:
                 return lib.mipx_op_rgb_to_jpeg_scan_optimized(X, Y, n, w, h, layout, a.q, WS, sp)
             return lib.mipx_op_rgb_to_jpeg_scan(X, Y, n, w, h, layout, a.q, WS, sp)
-        if a.op in ("jpegcs420", "jpegcs444"):
+        if a.op in ("jpegcs420", "jpegcs444", "jpegcsgrey"):
             if a.optimize:
                 return lib.mipx_op_jpegc_to_scan_optimized(X, Y, n, w, h, layout, WS, sp)
             return lib.mipx_op_jpegc_to_scan(X, Y, n, w, h, layout, WS, sp)
-        if a.op in ("jpegh420", "jpegh444", "jpegh422"):
+        if a.op in ("jpegh420", "jpegh444", "jpegh422", "jpeghgrey"):
             return lib.mipx_op_jpegh_to_rgb(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
-        if a.op in ("jpeghd420", "jpeghd444", "jpeghd422"):
+        if a.op in ("jpeghd420", "jpeghd444", "jpeghd422", "jpeghdgrey"):
             return lib.mipx_op_jpegh_to_jpegd(X, Y, status.data_ptr(), n, w, h, layout, WS, WSB, sp)
         raise SystemExit(a.op)
 
@@ -364,7 +379,7 @@ def main():
                 line.update(restart=a.restart, restart_mcus=int(x.view(n, in_img)[0, 4:8].cpu().numpy().view("<u4")[0]))
             line.update(q=a.q, file=os.path.basename(a.file), capacity=in_img - 1504,
                         mean_length=round(float(lengths.mean()), 1), upload_bytes=round(1504 + float(lengths.mean()), 1),
-                        rgb_bytes=w * h * 3, statuses=sorted(set(status.cpu().tolist())))
+                        rgb_bytes=w * h * pb, statuses=sorted(set(status.cpu().tolist())))
         print(json.dumps({**line, "ms": round(ms, 4), "alg_GBps": round(alg / ms / 1e6, 1)}))
         return
     # same-process A/B: --ab KNOB=v1,v2,... interleaved over 2 rounds, output checked equal
